@@ -18,6 +18,11 @@ Weights: random init (no network); rank 0's compiled weights are RCCL-broadcast 
 other rank (the DP model-distribution path).  A "step" is one micro-batch of --batch
 records per GPU (weak scaling).  W warmup steps, then exactly K timed steps bracketed by a
 barrier + device synchronize; the elapsed time is the MAX over ranks.
+
+A plain run does only that: set up, warm up, time the K steps, print one JSON line
+(``ms_per_step`` = elapsed / K).  ``--dump-outputs DIR`` adds the last timed step's fetched
+arrays as ``DIR/<name>.npy`` (records, weights and batch sizes are seeded: the same arguments
+give the same inputs); ``--full`` is where measurements beyond the headline figure belong.
 """
 from __future__ import annotations
 
@@ -70,6 +75,27 @@ def self_launch(args) -> int | None:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on this host driver
     return subprocess.call(cmd, env=env)
+
+
+def dump_outputs(out_dir, rank, arrays):
+    """``--dump-outputs``: each array of the last timed step as ``<name>.npy`` (float32;
+    float64 stays float64; integer class ids are exact in float32), rank r > 0 as
+    ``<name>.rank<r>.npy``.  At most 64 MB in all: a larger array is cut to a fixed, seeded
+    sample of its elements."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (64 << 20) // max(1, len(arrays))
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+        if a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
 
 
 def run_launch_check(args, comm, rank, ws):
@@ -162,8 +188,23 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, rendezvous, exchange one object per rank and print the world the "
                          "communicator sees (no model; with --rehearse-fake-comm it runs on a CPU-only box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (the "
+                         "fetched arrays of its micro-batch, valid rows only; widedeep: the step's loss) as "
+                         "DIR/<name>.npy in float32 / float64 (rank r > 0: DIR/<name>.rank<r>.npy).  Records, "
+                         "weights and batch sizes are seeded, so two builds run with the same arguments can be "
+                         "compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure (baselines, other "
+                         "configurations, reference comparisons).  The plain run already does only what the "
+                         "result line needs — set up, warm up, time --steps steps, print — and every other "
+                         "measurement is a mode of its own (--model, --job, --offered-rate, --dynamic, "
+                         "--timeline, ...), so today --full adds nothing to it")
     args = ap.parse_args()
 
+    if args.dump_outputs and (args.job or args.offered_rate or args.launch_check):
+        raise SystemExit("[bench] --dump-outputs: the closed-loop stream and widedeep steps only (in --job mode "
+                         "results stay in the workers; --offered-rate batches form by wall-clock arrival)")
     if args.job:
         return run_job(args)
     rc = self_launch(args)
@@ -349,9 +390,10 @@ def main():
     n_done = 0
     n_sub = 0
     size_rng = np.random.default_rng(99)
+    last = None  # the newest result (results come back in submission order): --dump-outputs
 
     def step(collect):
-        nonlocal cursor, n_done, n_sub
+        nonlocal cursor, n_done, n_sub, last
         n = int(size_rng.integers(max(1, B // 4), B + 1)) if args.dynamic else B
         batch = [records[(cursor + i) % args.pool] for i in range(n)]
         cursor += n
@@ -366,6 +408,7 @@ def main():
             n_done += r.n
             if collect:
                 lat.append(r.latencies[: r.n])
+                last = r
 
     for _ in range(args.warmup):
         step(False)
@@ -380,11 +423,19 @@ def main():
         step(True)
     for r in runner.drain():
         lat.append(r.latencies[: r.n])
+        last = r
     torch.cuda.synchronize(dev)
     comm.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t_start
     elapsed_max = comm.all_reduce_scalar(elapsed, "max", device=dev)
+    if args.dump_outputs:
+        if last is None:
+            raise SystemExit("[bench] --dump-outputs needs at least one timed step")
+        fetches = {"resnet50": ["top_k_0", "top_k_1"], "inception_v3": ["top_k_0", "top_k_1"],
+                   "bert_graph": ["logits_0"]}.get(args.model, [])
+        dump_outputs(args.dump_outputs, rank, {(fetches[i] if i < len(fetches) else f"output_{i}"): t[: last.n]
+                                               for i, t in enumerate(last.outputs)})
 
     lat_all = np.concatenate(lat) if lat else np.zeros(1)
     # node-level percentiles: per-rank latency histograms merged bucket-wise (one all-reduce)
@@ -781,6 +832,10 @@ def run_widedeep(args, dev, rank, ws):
     elapsed = time.perf_counter() - t_start
     elapsed_max = comm.all_reduce_scalar(elapsed, "max", device=dev)
     total = ws * B * args.steps / elapsed_max
+    if args.dump_outputs:
+        if loss is None:
+            raise SystemExit("[bench] --dump-outputs needs at least one timed step")
+        dump_outputs(args.dump_outputs, rank, {"loss": np.asarray(float(loss), dtype=np.float64)})
     ex = tr._exchange
     if ex is not None and hasattr(ex, "check"):
         ex.check()  # no bucket of the fixed-capacity exchange overflowed in the timed steps

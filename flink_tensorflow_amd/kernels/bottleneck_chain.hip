@@ -185,8 +185,12 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
   dma(t, 0);
   while (true) {
     const int p0 = t * TP;
-    // this tile's sources (issued one tile ago) and every older store have landed
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // this tile's sources (issued one tile ago) and every older store have landed; and this
+    // wave's O writes of the previous tile (phase 2, the last LDS writes before the loop's
+    // back edge) have too: the compiler's own lgkmcnt wait for this barrier is missing on the
+    // back edge, and a sibling wave's store_y1 below then read O before the write landed
+    // (seen only with a co-resident workgroup of another stream delaying the LDS queue)
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
     if (prev >= 0) store_y1(prev);  // O is read before phase 2 rewrites it (a barrier between)
     const int tn = t + gridDim.x;

@@ -106,6 +106,42 @@ def test_bench_refuses_missing_gpus():
     assert "refusing" in p.stderr
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """``bench.py --dump-outputs``: every array lands as ``<name>.npy`` in float32 (float64
+    kept), other ranks under their own names, and an array over the size cap is cut to the
+    same seeded sample every time."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_main", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    probs = torch.rand(6, 5, dtype=torch.bfloat16)
+    idx = torch.arange(30, dtype=torch.int32).reshape(6, 5)
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), 0, {"top_k_0": probs, "top_k_1": idx, "loss": np.asarray(0.25, np.float64)})
+    bench.dump_outputs(str(d), 3, {"top_k_1": idx})
+    assert sorted(p.name for p in d.iterdir()) == ["loss.npy", "top_k_0.npy", "top_k_1.npy", "top_k_1.rank3.npy"]
+    a, b, c = np.load(d / "top_k_0.npy"), np.load(d / "top_k_1.npy"), np.load(d / "loss.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32 and c.dtype == np.float64 and c == 0.25
+    np.testing.assert_array_equal(a, probs.float().numpy())
+    np.testing.assert_array_equal(b, idx.numpy().astype(np.float32))
+    big = torch.arange((64 << 20) // 8 + 1000, dtype=torch.float64)
+    bench.dump_outputs(str(d), 0, {"big": big})
+    bench.dump_outputs(str(tmp_path / "again"), 0, {"big": big})
+    s = np.load(d / "big.npy")
+    assert s.nbytes == 64 << 20 and np.all(np.diff(s) > 0)  # a sample of distinct elements, in order
+    np.testing.assert_array_equal(s, np.load(tmp_path / "again" / "big.npy"))
+
+
+def test_bench_has_full_and_dump_outputs_options():
+    """``--full`` and ``--dump-outputs`` are part of the benchmark's command line."""
+    p = _bench("--help", timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
 def test_sysfs_gpu_count_reads_kfd_topology(tmp_path, monkeypatch):
     """GPUs are counted from the KFD topology (nodes with SIMDs), narrowed by a visibility
     mask, without loading any GPU library."""
