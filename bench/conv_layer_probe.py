@@ -1,11 +1,8 @@
 """One ResNet-50 layer shape per process for counter runs (``rocprofv3 --pmc``): the
-incumbent implicit-GEMM conv (``igemm``) and the ping-pong conv (``pp``) on the stage 2/3/4
-3x3 layers at B=256, --reps launches each, plus a µs line per kernel on stdout.
+register-staged implicit-GEMM conv (``igemm``) and the 4-wave LDS-DMA conv (``lite``) on the
+stage 2/3/4 3x3 layers at B=256, --reps launches each, plus a µs line per kernel on stdout.
 
-    python bench/conv_layer_probe.py --layers s3_3x3 --impls igemm,lite:2,lite:4,lite:5,lite:6 --reps 10
-
-(``lite:4`` / ``5`` / ``6``: tile 2 without MFMAs / without DMA after the first K-tile /
-MFMAs only — a decomposition of where its time goes; outputs meaningless.)
+    python bench/conv_layer_probe.py --layers s3_3x3 --impls igemm,lite --reps 10
 """
 import argparse
 import json
@@ -54,13 +51,14 @@ def main():
             if impl == "igemm":
                 def fn():
                     K.conv2d_nhwc(x, w, b, res, (s, s), (pad, pad, pad, pad), (1, 1), K.ACT_RELU, out=y)
-            else:  # lite[:tile]: the 128x128 LDS-DMA tile (2; 4..6 diagnostics)
-                tile = int(impl.split(":")[1]) if ":" in impl else None
-                cp = K.ConvPP([((B, H, W, Cin), (k, k), (s, s), (pad, pad), (1, 1))], Cout, (OH, OW), dev, tile=tile)
+            elif impl == "lite":  # the 128x128 LDS-DMA tile
+                cp = K.ConvPP([((B, H, W, Cin), (k, k), (s, s), (pad, pad), (1, 1))], Cout, (OH, OW), dev)
                 w2 = w.reshape(Cout, -1)
 
                 def fn(cp=cp, w2=w2):
                     cp([x], w2, b, res, K.ACT_RELU, out=y)
+            else:
+                raise SystemExit(f"unknown impl {impl!r}: igemm or lite")
             fn()
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -69,15 +69,14 @@ def _cfg():
 
     return current()
 
-# conv_lite tiles (kernels/conv_pp.hip): bf16 tile 2 = 128 pixels x 128 channels on 4 waves,
-# two LDS-DMA stages; fp8 cfg 11 = the channel tile (192 / 160 / 128 / 96 / 64) staging the
+# conv_lite tiles (kernels/conv_pp.hip): bf16 = 128 pixels x 128 channels on 4 waves, two
+# LDS-DMA stages (the only bf16 tile left); fp8 cfg 11 = the channel tile (192 / 160 / 128 / 96 / 64) staging the
 # fewest rows per layer (profiles/r04_af).  Measured slower and removed (numbers in the
 # profile READMEs): the 128x256 bf16 tile (r04_ad), the 8-wave DMA / MFMA-split tiles (r04_u,
 # r04_w), the halo-staged 3x3 kernel (r04_s-u), the 32-deep tile, the fp8 tile choosers
 # 0 / 1 / 3 (r04_ac, r04_ah), conv_lite for the deep-K 1x1 reduces (r03_conv), the streamed
 # stage-2 block tail (r01_tail), the persistent dual projection kernel (r02_pw_res2) and the
 # probe-selected ping-pong conv_pp tiles (r02_conv_pp).
-LITE_TILE = 2
 LITE_FP8_CFG = 11
 
 
@@ -898,8 +897,8 @@ class CompiledFunction(TransformerLowering):
             # (kernels/conv_pp.hip conv_lite): 6-24 % faster than the register-staged igemm
             # per layer and 64 KiB of LDS, so it shares a CU with the sibling lane
             cl = K.ConvPP([(tuple(xin.shape), (KHe, KWe), (sh, sw), (pt, pl), (dh, dw))], Cout, tuple(out.shape[1:3]),
-                          self.device, tile=LITE_TILE)  # tiles 3 (32-deep K), 256x128 (4 or 8 waves) and 3-stage
-            # variants (raw-barrier, counted vmcnt) measured slower: profiles/r03_conv, r04_a, r04_c
+                          self.device)  # the 32-deep-K tile, 256x128 (4 or 8 waves) and 3-stage variants
+            # (raw-barrier, counted vmcnt) measured slower: profiles/r03_conv, r04_a, r04_c
 
             def run(xin=xin, out=out, res_val=res_val, cl=cl, w2=w_dev.reshape(Cout, -1), b_dev=b_dev):  # noqa: F811
                 cl([xin.buf], w2, b_dev, res_val.buf if res_val is not None else None, act, out=_target(out),
@@ -970,11 +969,11 @@ class CompiledFunction(TransformerLowering):
             # stage 2's 200k-row GEMM stays on the igemm (141 vs 158 µs, profiles/r03_operating_points)
             xs0 = (tuple(xin.shape), (1, 1), (1, 1), (0, 0), (1, 1))
             lite = {s2: K.ConvPP([xs0, (tuple(x2.shape), (1, 1), (s2, s2), (0, 0), (1, 1))], Cout, (Ho, Wo),
-                                 self.device, tile=LITE_TILE)}
+                                 self.device)}
             N2, H2, W2, _ = x2.shape
             if s2 == 2 and H2 % 2 == 0 and W2 % 2 == 0:
                 lite[1] = K.ConvPP([xs0, ((N2, H2 // 2, W2 // 2, C2), (1, 1), (1, 1), (0, 0), (1, 1))], Cout, (Ho, Wo),
-                                   self.device, tile=LITE_TILE)
+                                   self.device)
 
             def run(xin=xin, x2=x2, out=out, w_dev=w_dev, b_dev=b_dev, s2cfg=s2cfg, lite=lite):  # noqa: F811
                 lite[s2cfg["s2"]]([xin.buf, x2.buf], w_dev, b_dev, None, act, out=_target(out),

@@ -429,25 +429,6 @@ void embed_ln_bf16(uintptr_t ids, uintptr_t tt, uintptr_t pos_ids, uintptr_t wor
   FTM_CHECK_LAUNCH();
 }
 
-// Diagnostic: LDS[r][c] = r * 256 + c (16-bit, 16 rows x 64 cols); every lane issues one
-// transposed read at (row = 4*(lane>>4) + ((lane&15)>>2), col = 4*(lane&3) + 16*blk);
-// out[lane][0..3] = the 4 returned elements.
-__global__ void probe_tr_kernel(short* out, int blk) {
-  __shared__ __attribute__((aligned(16))) short t[16 * 64];
-  for (int i = threadIdx.x; i < 16 * 64; i += 64) t[i] = (short)((i / 64) * 256 + (i % 64));
-  __syncthreads();
-  const int lane = threadIdx.x;
-  const int row = 4 * (lane >> 4) + ((lane & 15) >> 2), col = 4 * (lane & 3) + 16 * blk;
-  v4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(t + row * 64 + col));
-  for (int e = 0; e < 4; ++e) out[lane * 4 + e] = v[e];
-}
-
-void probe_tr_read(uintptr_t out, int blk, uintptr_t stream) {
-  hipLaunchKernelGGL(probe_tr_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<short*>(out), blk);
-  FTM_CHECK_LAUNCH();
-}
-
 void cls_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale,
                         uintptr_t stream) {
   if (Dh != D) throw std::invalid_argument("cls_attention: head dim must be 64");
@@ -462,7 +443,6 @@ void cls_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H
 
 void register_attention(pybind11::module_& m) {
   m.def("cls_attention_bf16", &cls_attention_bf16);
-  m.def("probe_tr_read", &probe_tr_read);
   m.def("attention_fwd_bf16", &attention_fwd_bf16);
   m.def("embed_ln_bf16", &embed_ln_bf16);
   m.def("pack_tokens", &pack_tokens);

@@ -384,10 +384,6 @@ int lds_bytes(int es, int bn, int KH, int KW, int S, int Cin, int wp, bool pool,
   return need > epi ? need : epi;
 }
 
-int dconv_lds_bytes(int es, int bn, int KH, int KW, int S, int Cin, int wp) {
-  return lds_bytes(es, bn, KH, KW, S, Cin, wp, false);
-}
-
 // x: NHWC (bf16 es=2 / e4m3 es=1); w: host-arranged [Cout_pad][wp] bytes.
 void dconv(uintptr_t x, uintptr_t w, uintptr_t scale, uintptr_t bias, uintptr_t y, int es, int N, int H, int W,
            int Cin, int Cout, int KH, int KW, int S, int ph, int pw, int Ho, int Wo, int wp, int ldy, int y_coff,
@@ -540,5 +536,4 @@ void dconv_u8s2d(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int N, i
 void register_dconv(pybind11::module_& m) {
   m.def("dconv", &dconv);
   m.def("dconv_u8s2d", &dconv_u8s2d);
-  m.def("dconv_lds_bytes", &dconv_lds_bytes);
 }

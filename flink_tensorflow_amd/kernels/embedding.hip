@@ -298,23 +298,6 @@ __global__ __launch_bounds__(256) void segsum_fixup_kernel(const int* __restrict
   }
 }
 
-// Segment boundaries of a sorted key array, static shapes: for every i that starts a run
-// (i == 0 or sorted[i] != sorted[i-1]) with run index s = seg_id[i]:  seg[s] = i and
-// uids[s] = key (or -1 for the invalid bucket key == num_rows).  Each run is written by
-// exactly one thread: deterministic, no atomics, no host round trip.
-__global__ __launch_bounds__(256) void segment_starts_kernel(const int* __restrict__ sorted,
-                                                             const int* __restrict__ seg_id, int* __restrict__ seg,
-                                                             int* __restrict__ uids, int n, int num_rows) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int k = sorted[i];
-  if (i == 0 || sorted[i - 1] != k) {
-    const int sidx = seg_id[i];
-    seg[sidx] = i;
-    uids[sidx] = k >= num_rows ? -1 : (int)k;
-  }
-}
-
 // G = D/4 lanes per touched row (a power of two <= 64), 4 elements per lane.
 __global__ __launch_bounds__(256) void sparse_adagrad_kernel(float* __restrict__ table, float* __restrict__ accum,
                                                              const int* __restrict__ uids, const float* __restrict__ g,
@@ -576,16 +559,6 @@ void segment_sum_sorted(uintptr_t grad, uintptr_t perm, uintptr_t seg_id, uintpt
   FTM_CHECK_LAUNCH();
 }
 
-void segment_starts(uintptr_t sorted, uintptr_t seg_id, uintptr_t seg, uintptr_t uids, int n, long long num_rows,
-                    uintptr_t stream) {
-  if (n <= 0) return;
-  if (num_rows >= (1LL << 31) - 1) throw std::invalid_argument("segment_starts: num_rows must fit int32");
-  hipLaunchKernelGGL(segment_starts_kernel, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const int*>(sorted), reinterpret_cast<const int*>(seg_id),
-                     reinterpret_cast<int*>(seg), reinterpret_cast<int*>(uids), n, (int)num_rows);
-  FTM_CHECK_LAUNCH();
-}
-
 static void rows_move(bool gather, uintptr_t table, uintptr_t ids, uintptr_t rows, long long n, int D, int V,
                       uintptr_t stream) {
   if (D % 4) throw std::invalid_argument("rows_gather/scatter: D % 4 != 0");
@@ -634,7 +607,6 @@ void register_embedding(pybind11::module_& m) {
   m.def("owner_buckets_segments", &owner_buckets_segments);
   m.def("rows_gather", &rows_gather);
   m.def("rows_scatter", &rows_scatter);
-  m.def("segment_starts", &segment_starts);
   m.def("embedding_bag_fwd", &embedding_bag_fwd);
   m.def("segment_sum_rows", &segment_sum_rows);
   m.def("segment_sum_sorted", &segment_sum_sorted);

@@ -7,11 +7,10 @@
 //   wd_loss       logit = deep[b] + wsum[b] + wide_bias, BCE-with-logits mean (block partials
 //                 added in block order), dlogit = (sigmoid - y) / B, wide gradient rows, the
 //                 scalar gradients (wide bias, head bias 0)
-//   wd_head_bwd   dh[b, j] = (h[b, j] > 0) * dlogit[b] * w_head0[j]   (bf16)
+//   wd_head_bwd2  dh[b, j] = (h[b, j] > 0) * dlogit[b] * w_head0[j]   (bf16), with the column
+//                 partials of the top layer's bias gradient and of the head weight row
 //   wd_adam       Adam over the flat fp32 parameter buffer (device step counter, so a
 //                 captured step replays correctly) + the bf16 copy of every weight segment
-//   wd_mask_colsum  the ReLU backward mask of a layer input, in place on the library dX,
-//                 and the bias gradient (column sums, fixed order) in the same pass
 #include <pybind11/pybind11.h>
 
 #include <stdexcept>
@@ -171,21 +170,6 @@ __global__ __launch_bounds__(64) void wd_loss_final_kernel(const float* __restri
   }
 }
 
-__global__ __launch_bounds__(256) void wd_head_bwd_kernel(const bf16* __restrict__ h, const float* __restrict__ dlogit,
-                                                          const float* __restrict__ wh0, bf16* __restrict__ dh, int B,
-                                                          int H) {
-  const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  const int cpr = H >> 3;
-  if (t >= (long)B * cpr) return;
-  const int b = (int)(t / cpr), c = (int)(t - (long)b * cpr) * 8;
-  const float d = dlogit[b];
-  const bf16x8 hv = *reinterpret_cast<const bf16x8*>(h + (size_t)b * H + c);
-  bf16x8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf((float)hv[e] > 0.f ? d * wh0[c + e] : 0.f);
-  *reinterpret_cast<bf16x8*>(dh + (size_t)b * H + c) = o;
-}
-
 // Head backward in one pass over the top hidden activations h [B, H] (only logit column 0
 // of the 8-row head is used): dh = (h > 0) ? dlogit[b] * wh0 : 0 (bf16), plus this block's
 // column partials of dh (-> the top layer's bias gradient) and of dlogit[b] * h (-> the head
@@ -256,46 +240,6 @@ __global__ __launch_bounds__(256) void wd_adam_kernel(float* __restrict__ p, con
   }
 }
 
-// db[j] = sum_b x[b, j] (fp32, fixed order), optionally after the ReLU backward mask of the
-// layer input h (x[b, j] = 0 where h[b, j] <= 0, written back).  Block = 16 columns x 128
-// row lanes; each lane sums every 128th row of its 8 columns, then a fixed LDS tree.
-__global__ __launch_bounds__(256) void wd_mask_colsum_kernel(bf16* __restrict__ x, const bf16* __restrict__ h,
-                                                             float* __restrict__ db, int B, int n) {
-  __shared__ float red[128][17];
-  const int chunk = threadIdx.x & 1;      // which 8 of the block's 16 columns
-  const int rl = threadIdx.x >> 1;        // row lane 0..127
-  const int c0 = blockIdx.x * 16 + chunk * 8;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (c0 < n) {
-    for (int b = rl; b < B; b += 128) {
-      bf16x8* px = reinterpret_cast<bf16x8*>(x + (size_t)b * n + c0);
-      bf16x8 xv = *px;
-      if (h) {
-        const bf16x8 hv = *reinterpret_cast<const bf16x8*>(h + (size_t)b * n + c0);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) xv[e] = (float)hv[e] > 0.f ? xv[e] : f2bf(0.f);
-        *px = xv;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += (float)xv[e];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[rl][chunk * 8 + e] = acc[e];
-  __syncthreads();
-  for (int w = 64; w > 0; w >>= 1) {
-    if (rl < w) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[rl][chunk * 8 + e] += red[rl + w][chunk * 8 + e];
-    }
-    __syncthreads();
-  }
-  if (rl == 0 && c0 < n) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) db[c0 + e] = red[0][chunk * 8 + e];
-  }
-}
-
 int pow2_shift(int g) {
   for (int k = 0; k <= 6; ++k)
     if (g == (1 << k)) return k;
@@ -363,17 +307,6 @@ void wd_loss(uintptr_t head, int ldh, uintptr_t wsum, uintptr_t wbias, uintptr_t
   FTM_CHECK_LAUNCH();
 }
 
-void wd_head_bwd(uintptr_t h, uintptr_t dlogit, uintptr_t wh0, uintptr_t dh, int B, int H, uintptr_t stream) {
-  if (H % 8 || h % 16 || dh % 16) throw std::invalid_argument("wd_head_bwd: H % 8 and 16-byte alignment");
-  const long work = (long)B * (H / 8);
-  if (work <= 0) return;
-  hipLaunchKernelGGL(wd_head_bwd_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const bf16*>(h),
-                     reinterpret_cast<const float*>(dlogit), reinterpret_cast<const float*>(wh0),
-                     reinterpret_cast<bf16*>(dh), B, H);
-  FTM_CHECK_LAUNCH();
-}
-
 void wd_head_bwd2(uintptr_t h, uintptr_t dlogit, uintptr_t wh0, uintptr_t dh, uintptr_t part, int B, int H, int blocks,
                   uintptr_t stream) {
   if (H % 8 || H > 2048 || 256 % (H / 8) || h % 16 || dh % 16 || wh0 % 16)
@@ -398,20 +331,10 @@ void wd_adam(uintptr_t p, uintptr_t g, uintptr_t m, uintptr_t v, long n, uintptr
   FTM_CHECK_LAUNCH();
 }
 
-void wd_mask_colsum(uintptr_t x, uintptr_t h, uintptr_t db, int B, int n, uintptr_t stream) {
-  if (n % 8 || x % 16 || h % 16) throw std::invalid_argument("wd_mask_colsum: n % 8 and 16-byte alignment");
-  if (B <= 0 || n <= 0) return;
-  hipLaunchKernelGGL(wd_mask_colsum_kernel, dim3((n + 15) / 16), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<bf16*>(x), reinterpret_cast<const bf16*>(h), reinterpret_cast<float*>(db), B, n);
-  FTM_CHECK_LAUNCH();
-}
-
 void register_widedeep(pybind11::module_& m) {
   m.def("wd_gather", &wd_gather);
   m.def("wd_loss", &wd_loss);
   m.def("wd_keys", &wd_keys);
-  m.def("wd_head_bwd", &wd_head_bwd);
   m.def("wd_head_bwd2", &wd_head_bwd2);
   m.def("wd_adam", &wd_adam);
-  m.def("wd_mask_colsum", &wd_mask_colsum);
 }

@@ -583,31 +583,22 @@ def gemm_pp(x: torch.Tensor, w_nk: torch.Tensor, bias: torch.Tensor | None = Non
     return out
 
 
-def conv_pp_ktab(srcs) -> torch.Tensor:
-    """Host-built K-tile table of ``conv_pp``: for every 64-wide K tile (source, kh, kw,
-    channel chunk order) the byte delta of its input rows relative to the receptive-field
-    origin, and ``src << 20 | kh*dh << 10 | kw*dw``.  ``srcs``: (H, W, C, KH, KW, dh, dw)."""
-    rows = []
-    for si, (H, W, C, KH, KW, dh, dw) in enumerate(srcs):
-        for kh in range(KH):
-            for kw in range(KW):
-                for cc in range(C // 64):
-                    rows.append((((kh * dh * W + kw * dw) * C + cc * 64) * 2, (si << 20) | (kh * dh << 10) | (kw * dw)))
-    return torch.tensor(rows, dtype=torch.int32)
-
-
 class ConvPP:
     """A planned ``conv_lite`` launch (kernels/conv_pp.hip): implicit-GEMM NHWC convolution
-    of one or two sources into one accumulator on the 4-wave 128x128 LDS-DMA tile (``tile``
-    2; 4..6 are diagnostic variants).  The ping-pong / wide / wave-split / two-wave /
-    deeper-prefetch tiles measured slower and were removed (``kernels/conv_pp.hip``).
+    of one or two sources into one accumulator on the 4-wave 128x128 LDS-DMA tile, the only
+    tile: the ping-pong / wide / wave-split / two-wave / deeper-prefetch tiles and split-K
+    measured slower and were removed (``kernels/conv_pp.hip``).
 
     ``srcs``: [(x_shape NHWC, (KH, KW), (sh, sw), (pt, pl), (dh, dw))]; the weight is the
     concatenation of the sources' OHWI filters, [Cout, sum KH*KW*C] bf16; a second source
-    must be 1x1, unpadded and in range (a projection shortcut).  The K-tile table is built
-    once (a device tensor kept on the object)."""
+    must be 1x1, unpadded and in range (a projection shortcut).  The plan holds shapes only:
+    nothing is allocated on ``device``.  ``tile`` / ``splits`` no longer select anything:
+    a caller written against the earlier signature may still pass ``None`` (it meant "the
+    default"); any value is a ``TypeError``."""
 
-    def __init__(self, srcs, Cout: int, out_hw, device, tile: int | None = None, splits: int | None = None):
+    def __init__(self, srcs, Cout: int, out_hw, device, tile: None = None, splits: None = None):
+        if tile is not None or splits is not None:
+            raise TypeError("conv_pp: the tile and splits arguments are gone (one tile, no split-K)")
         self.srcs = [(tuple(xs), tuple(k), tuple(st), tuple(pd), tuple(dl)) for xs, k, st, pd, dl in srcs]
         self.N = self.srcs[0][0][0]
         self.OH, self.OW = out_hw
@@ -619,24 +610,15 @@ class ConvPP:
         if Cout % 8:
             raise ValueError("conv_pp: Cout % 8")
         self.M = self.N * self.OH * self.OW
-        self.tile = 2 if tile is None else tile
-        # (4..6: diagnostic variants for bench/conv_layer_probe.py, outputs meaningless)
-        if self.tile not in (2, 4, 5, 6) or (splits or 1) != 1 or (self.tile != 2 and len(self.srcs) != 1):
-            raise ValueError("conv_pp: only the conv_lite tile (2) without split-K remains")
         if len(self.srcs) == 2:
             (xs1, k1, st1, pd1, dl1) = self.srcs[1]
             if tuple(k1) != (1, 1) or tuple(pd1) != (0, 0) or (self.OH - 1) * st1[0] >= xs1[1] \
                     or (self.OW - 1) * st1[1] >= xs1[2]:
                 raise ValueError("conv_pp: the 4-wave tile's second source must be 1x1, unpadded, in range")
-        self.splits = 1
-        self.ktab = conv_pp_ktab([(xs[1], xs[2], xs[3], k[0], k[1], dl[0], dl[1])
-                                  for xs, k, _, _, dl in self.srcs]).to(device)
-        self.ws = (torch.empty(self.splits * self.M * Cout, dtype=torch.float32, device=device)
-                   if self.splits > 1 else None)
 
     def for_batch(self, n: int) -> "ConvPP":
         """The same convolution planned for ``n`` images (a batch slice: the compiler's
-        batch-slice chain); shares the K-tile table and the split-K workspace."""
+        batch-slice chain); cached per ``n`` on the full-batch plan."""
         if n == self.N:
             return self
         subs = self.__dict__.setdefault("_subs", {})
@@ -679,9 +661,8 @@ class ConvPP:
                 raise ValueError("conv_pp: residual shape")
         srcs = [(x.data_ptr(), self.N, sh[1], sh[2], sh[3], k[0], k[1], st[0], st[1], pd[0], pd[1], dl[0], dl[1])
                 for x, (sh, k, st, pd, dl) in zip(xs, self.srcs)]
-        _hip().conv_pp(srcs, self.ktab.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                       self.N, self.OH, self.OW, self.Cout, ldy, out_channel_offset, self.Cout, act_code(act),
-                       self.tile, self.splits, _ptr(self.ws), _stream())
+        _hip().conv_pp(srcs, w.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), self.N, self.OH, self.OW,
+                       self.Cout, ldy, out_channel_offset, self.Cout, act_code(act), _stream())
         return out
 
     def _reference(self, xs, w, bias, residual, act, out, coff):

@@ -1,8 +1,8 @@
-"""``conv_pp`` (kernels/conv_pp.hip): implicit-GEMM NHWC convolution on the ping-pong MFMA
-pipeline, checked against a plain PyTorch fp32 convolution of the same bf16 operands —
-3x3 / 1x1 / strided / dilated / asymmetric (1x7, 7x1) filters, both tile shapes, M tails,
-split-K, residual + ReLU epilogue, concat channel offsets and the dual-source (conv +
-strided projection shortcut) mode."""
+"""``conv_pp`` (kernels/conv_pp.hip): implicit-GEMM NHWC convolution on the 4-wave 128x128
+LDS-DMA tile (conv_lite), checked against a plain PyTorch fp32 convolution of the same bf16
+operands — 3x3 / 1x1 / strided / dilated / asymmetric (1x7, 7x1) filters, M and N tails,
+residual + ReLU epilogue, concat channel offsets and the dual-source (conv + strided
+projection shortcut) mode with and without a residual."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -45,10 +45,15 @@ CASES = [
                    ((2, 28, 28, 256), (1, 1), (2, 2), (0, 0), (1, 1))], 512, (14, 14), False, "relu"),
     ("lite_dual_s1", [((3, 7, 7, 64), (1, 1), (1, 1), (0, 0), (1, 1)),
                       ((3, 7, 7, 128), (1, 1), (1, 1), (0, 0), (1, 1))], 200, (7, 7), False, None),
+    # two sources + residual, both activations: one M tile with a tail (98 rows), N tail (136)
+    ("lite_dual_res_relu", [((2, 7, 7, 64), (1, 1), (1, 1), (0, 0), (1, 1)),
+                            ((2, 14, 14, 64), (1, 1), (2, 2), (0, 0), (1, 1))], 136, (7, 7), True, "relu"),
+    ("lite_dual_res", [((2, 7, 7, 64), (1, 1), (1, 1), (0, 0), (1, 1)),
+                       ((2, 14, 14, 64), (1, 1), (2, 2), (0, 0), (1, 1))], 136, (7, 7), True, None),
 ]
 
 
-def _run(case, dev, coff=0, tile=None):
+def _run(case, dev, coff=0):
     name, srcs, Cout, (OH, OW), with_res, act = case
     torch.manual_seed(0)
     xs = [torch.randn(s[0], device=dev).to(torch.bfloat16) for s in srcs]
@@ -57,7 +62,7 @@ def _run(case, dev, coff=0, tile=None):
     bias = torch.randn(Cout, device=dev)
     N = srcs[0][0][0]
     res = torch.randn(N, OH, OW, Cout, device=dev).to(torch.bfloat16) if with_res else None
-    cp = K.ConvPP(srcs, Cout, (OH, OW), dev, tile=tile)
+    cp = K.ConvPP(srcs, Cout, (OH, OW), dev)
     out = torch.zeros(N, OH, OW, Cout + coff, dtype=torch.bfloat16, device=dev)
     cp(xs, w, bias, res, act, out=out, out_channel_offset=coff)
     ref = _ref(srcs, xs, w, bias, res, act, OH, OW)
@@ -86,12 +91,10 @@ def test_conv_pp_concat_offset_gpu():
     assert (left == 0).all()  # channels before the slice untouched
 
 
-def test_removed_tiles_are_refused():
-    with pytest.raises(ValueError):
-        K.ConvPP([((2, 14, 14, 64), (3, 3), (1, 1), (1, 1), (1, 1))], 64, (14, 14), "cpu", tile=0)
-
-
-def test_diagnostic_tiles_refuse_two_sources():
-    with pytest.raises(ValueError):
-        K.ConvPP([((2, 14, 14, 128), (1, 1), (1, 1), (0, 0), (1, 1)),
-                  ((2, 28, 28, 256), (1, 1), (2, 2), (0, 0), (1, 1))], 512, (14, 14), "cpu", tile=4)
+def test_removed_tiles_and_split_k_are_refused():
+    """The other tiles and split-K are gone with their arguments: the plan takes neither."""
+    src = [((2, 14, 14, 64), (3, 3), (1, 1), (1, 1), (1, 1))]
+    with pytest.raises(TypeError):
+        K.ConvPP(src, 64, (14, 14), "cpu", tile=0)
+    with pytest.raises(TypeError):
+        K.ConvPP(src, 64, (14, 14), "cpu", splits=2)
