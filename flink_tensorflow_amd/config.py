@@ -39,7 +39,7 @@ class EngineConfig:
     log_level: str = "INFO"
     # ---- compiler / kernel selection (FT_<NAME> env vars or YAML): every default is the
     # measured-fastest choice; these switch a fusion OFF for A/B runs.  Variants measured
-    # slower were removed with their kernels (graph/compiler.py LITE_FP8_CFG comment)
+    # slower were removed with their kernels (graph/conv_lowering.py LITE_FP8_CFG comment)
     sibling_conv_fusion: bool = True   # fp8: an Inception module's sibling 1x1 convs as one multi-output GEMM
     fuse_preprocess_stem: bool = True  # resize-free preprocess folded into the s2d RGB stem conv
     fuse_block_tails: bool = True      # ResNet block boundary: expand + next reduce in one kernel

@@ -43,6 +43,7 @@ import numpy as np
 import torch
 
 from ..ops import kernels as K
+from .plan import CompileError, Val, _view
 
 _ADDS = ("Add", "AddV2")
 _BMM = ("BatchMatMul", "BatchMatMulV2", "BatchMatMulV3")
@@ -289,7 +290,6 @@ class TransformerLowering:
         """Validates that the graph can run token-packed and finds the first-token-only region
         (``self._cls_nodes``); raises ``CompileError`` otherwise."""
         from ..types.names import TensorName
-        from .compiler import CompileError
 
         grps = list({id(g): g for g in self._groups.values()}.values())
         embs = [g for g in grps if g["kind"] == "emb"]
@@ -366,8 +366,6 @@ class TransformerLowering:
     def _cls_gather(self, v):
         """(B, D) rows of each sequence's first token of the packed ``v`` (one gather step,
         cached per value)."""
-        from .compiler import _view
-
         hit = self._cls_cache.get(id(v))
         if hit is not None:
             return hit
@@ -389,8 +387,6 @@ class TransformerLowering:
     def _reshape_rows(self, node, x, shape):
         """Reshape of packed / first-token rows: only the row split ([B*S, D] <-> [B, S, D])
         may change; the physical rows stay."""
-        from .compiler import CompileError, Val
-
         pk = self._pack
         D = x.shape[-1]
         n = pk["B"] * pk["S"] * D
@@ -404,8 +400,6 @@ class TransformerLowering:
         self.vals[(node.name, 0)] = Val(tuple(x.shape), x.dtype, alias_of=x, rows=x.rows, lshape=tuple(shape))
 
     def _slice_first_token(self, node, x) -> bool:
-        from .compiler import CompileError, Val
-
         if not self._first_token_spec(node) or x.lshape is None or len(x.lshape) != 3:
             raise CompileError(f"StridedSlice {node.name} of packed token rows is not a first-token slice")
         if x.rows == "packed":
@@ -496,7 +490,7 @@ class TransformerLowering:
             pk["cu"], pk["cls"] = cu, cls
 
             def run_pack(ids=ids32, pids=pids, ppos=ppos, cu=cu, cls=cls):
-                K.pack_tokens(_view_(ids).reshape(B, S), pk["pad"], T, pids.buf, ppos.buf, cu.buf, cls.buf)
+                K.pack_tokens(_view(ids).reshape(B, S), pk["pad"], T, pids.buf, ppos.buf, cu.buf, cls.buf)
 
             self._emit(grp["out"] + "/pack_tokens", "pack", run_pack, [ids32], [pids, ppos, cu, cls])
             out = self._new((T, D))
@@ -512,7 +506,7 @@ class TransformerLowering:
         out = self._new((B, S, D))
 
         def run(ids=ids32, out=out):
-            K.embed_layernorm(_view_(ids).reshape(-1), None, w_dev, pos_dev, typ_dev, g_dev, b_dev, S, eps,
+            K.embed_layernorm(_view(ids).reshape(-1), None, w_dev, pos_dev, typ_dev, g_dev, b_dev, S, eps,
                               out=out.buf.view(-1, D))
 
         self._emit(grp["out"], "embed_ln", run, [ids32], [out])
@@ -579,19 +573,20 @@ class TransformerLowering:
             else:
                 K.gemm(_rows(xin, Din), w_qkv, b_qkv, out=qkv.buf)
 
-        def run_attn(qkv=qkv, ctx=ctx, mask=mask):
-            K.attention(qkv.buf, _view_(mask).reshape(-1), B, S, nh, pad_id=0, scale=sc, out=ctx.buf)
-
         if pk is not None:
             cu = pk["cu"]
 
-            def run_attn(qkv=qkv, ctx=ctx, cu=cu):  # noqa: F811
+            def run_attn(qkv=qkv, ctx=ctx, cu=cu):
                 if cls_only:  # first query of each sequence only (the pooler reads nothing else)
                     K.cls_attention(qkv.buf, cu.buf, B, nh, scale=sc, out=ctx.buf)
                 else:
                     K.attention(qkv.buf, None, B, S, nh, scale=sc, out=ctx.buf, cu_seqlens=cu.buf)
 
             mask = cu
+        else:
+            def run_attn(qkv=qkv, ctx=ctx, mask=mask):
+                K.attention(qkv.buf, _view(mask).reshape(-1), B, S, nh, pad_id=0, scale=sc, out=ctx.buf)
+
         self._emit(grp["out"] + "/qkv", "gemm", run_qkv, [xin], [qkv], {"impl": "gemm_pp", "fused": "qkv"})
         self._emit(grp["out"], "cls_attention" if cls_only else "attention", run_attn, [qkv, mask], [ctx])
         self.vals[(grp["out"], 0)] = ctx
@@ -675,7 +670,7 @@ class TransformerLowering:
         sl = tuple(sl)
 
         def run(x=x, out=out, sl=sl):
-            out.buf.copy_(_view_(x)[sl].reshape(out.buf.shape))
+            out.buf.copy_(_view(x)[sl].reshape(out.buf.shape))
 
         self._emit(node.name, "copy", run, [x], [out])
         self.vals[(node.name, 0)] = out
@@ -701,17 +696,9 @@ class TransformerLowering:
             d = int(dv.reshape(-1)[0])
             d = d + len(shape) + 1 if d < 0 else d
             shape.insert(d, 1)
-        from .compiler import Val
-
         self.vals[(node.name, 0)] = Val(tuple(shape), x.dtype, alias_of=x)
         return True
 
 
-def _view_(v):
-    from .compiler import _view
-
-    return _view(v)
-
-
 def _rows(v, D):
-    return _view_(v).reshape(-1, D)
+    return _view(v).reshape(-1, D)
