@@ -578,7 +578,7 @@ class TransformerLowering:
 
             def run_attn(qkv=qkv, ctx=ctx, cu=cu):
                 if cls_only:  # first query of each sequence only (the pooler reads nothing else)
-                    K.cls_attention(qkv.buf, cu.buf, B, nh, scale=sc, out=ctx.buf)
+                    K.cls_attention(qkv.buf, cu.buf, B, S, nh, scale=sc, out=ctx.buf)
                 else:
                     K.attention(qkv.buf, None, B, S, nh, scale=sc, out=ctx.buf, cu_seqlens=cu.buf)
 

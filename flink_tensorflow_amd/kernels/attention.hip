@@ -212,7 +212,7 @@ __global__ __launch_bounds__(QB * 4) void attention_fwd_kernel(const bf16* __res
   }
 }
 
-// x[t] = LN(word[ids[t]] + pos[t % S] + type[tt[t]]) * gamma + beta   (D % 8 == 0, D <= 1024)
+// x[t] = LN(word[ids[t]] + pos[t % S] + type[tt[t]]) * gamma + beta   (D % 8 == 0, D <= 2048)
 template <int MAXV>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ ids, const int* __restrict__ tt,
                                                        const int* __restrict__ pos_ids,
@@ -324,7 +324,9 @@ __global__ __launch_bounds__(1024) void pack_tokens_kernel(const int* __restrict
 // classifier only needs each sequence's first row, so its attention is one query per
 // (sequence, head).  One wave per (b, h): lanes score keys (q . k_j, 64-d dot products from
 // 16-B loads), the softmax is a wave reduction, then lane d accumulates sum_j p_j v_j[d]
-// over coalesced 128-B V rows.  out [B, H*64] bf16.
+// over coalesced 128-B V rows.  out [B, H*64] bf16.  The scores of a sequence live in a
+// 512-float LDS row per wave: sequences are at most 512 keys long (ops.kernels.cls_attention
+// refuses a longer ``seq``); the min() below only keeps a bad cu_seqlens inside that row.
 __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restrict__ qkv, const int* __restrict__ cu,
                                                             bf16* __restrict__ out, int B, int H, float scale_log2e) {
   __shared__ float probs[4][512];
@@ -335,6 +337,10 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restri
   const int ld = 3 * H * D;
   const int t0 = cu[b];
   const int n = min(cu[b + 1] - t0, 512);
+  if (n <= 0) {  // empty sequence: a zero row, and row t0 (possibly one past the batch) is not read
+    out[(size_t)b * H * D + h * D + lane] = f2bf(0.f);
+    return;
+  }
   const bf16* qrow = qkv + (size_t)t0 * ld + h * D;
   float q[D];
 #pragma unroll

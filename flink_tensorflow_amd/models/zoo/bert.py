@@ -304,7 +304,7 @@ class BertEncoderPlan:
         B-row GEMMs run split-K through this buffer set's own workspace."""
         w, cfg = self.w, self.w.cfg
         ws = self.bufs.ws
-        K.cls_attention(self.qkv, self.cu, self.B, cfg.heads, out=self.c_ctx)
+        K.cls_attention(self.qkv, self.cu, self.B, self.S, cfg.heads, out=self.c_ctx)
         torch.index_select(self.x, 0, self.cls_idx, out=self.c_x)  # the layer input = residual
         K.gemm_pp(self.c_ctx, L["o_w"], L["o_b"], out=self.c_y, ws=ws)
         K.layernorm(self.c_y, L["ln1_g"], L["ln1_b"], residual=self.c_x, eps=cfg.eps, out=self.c_x2)

@@ -881,10 +881,19 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
     return out
 
 
-def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, heads: int, scale: float | None = None,
-                  out: torch.Tensor | None = None) -> torch.Tensor:
+CLS_ATTENTION_MAX_SEQ = 512  # keys per sequence the cls_attention kernel holds in LDS
+
+
+def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: int, heads: int,
+                  scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Attention of each packed sequence's FIRST token only (the classifier's final layer):
-    ``qkv`` [T, 3*H*64] packed rows, ``cu_seqlens`` [B+1] → [B, H*64]."""
+    ``qkv`` [T, 3*H*64] packed rows, ``cu_seqlens`` [B+1] → [B, H*64].  ``seq`` is the
+    longest possible sequence, as for ``attention``; the kernel keeps a sequence's scores in
+    LDS and handles at most 512 keys, so ``seq`` > 512 raises ``ValueError`` on the device
+    and on the host path alike (no sequence is ever silently truncated)."""
+    if seq > CLS_ATTENTION_MAX_SEQ:
+        raise ValueError(f"cls_attention: seq {seq} exceeds the {CLS_ATTENTION_MAX_SEQ} keys per sequence the "
+                         "kernel supports")
     Dh = qkv.shape[1] // (3 * heads)
     scale = (1.0 / Dh ** 0.5) if scale is None else scale
     if out is None:

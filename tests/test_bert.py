@@ -168,7 +168,7 @@ def test_packed_attention_and_pack_kernel_gpu(S):
                       cu_seqlens=douts[2])
     torch.testing.assert_close(got.float().cpu(), ref.float(), rtol=2e-2, atol=2e-2)
     # first-token-only attention == those rows of the full packed attention
-    cls_ref = K.cls_attention(qkv, outs[2], B, H)
-    cls_got = K.cls_attention(qkv.cuda(), douts[2], B, H)
+    cls_ref = K.cls_attention(qkv, outs[2], B, S, H)
+    cls_got = K.cls_attention(qkv.cuda(), douts[2], B, S, H)
     torch.testing.assert_close(cls_ref.float(), ref[outs[3].long()].float(), rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(cls_got.float().cpu(), cls_ref.float(), rtol=2e-2, atol=2e-2)
