@@ -10,14 +10,19 @@ Decode placements (``--decode``): ``staged`` (default) — the reader emits the 
 bytes (``ImageInputFormat(defer_decode=True)``) and the model's host stage decodes them with
 the native baseline decoder on its thread pool straight into the pinned staging slot
 (``csrc/jpeg.cpp``); the reader runs in the model's worker, with the directory listing too
-under ``--monitor partitioned`` (``sources.PartitionedFileSource``).  ``reader`` — Pillow
-decode in R reader worker processes, the reference's placement (``ImageInputFormat.scala``).
+under ``--monitor partitioned`` (``sources.PartitionedFileSource``).  ``device`` — as
+``staged``, but the host pool only entropy-decodes (Huffman) into pinned coefficient rows and
+the IDCT, upsampling and colour conversion run on the GPU (``kernels/jpeg.hip``,
+``jpeg_decode="device"``).  ``reader`` — Pillow decode in R reader worker processes, the
+reference's placement (``ImageInputFormat.scala``).
 
 Reports, as one JSON line:
 * records/s of the timed window on the model operator (W + K micro-batches,
   ``batching/timed.py``) and of the whole job;
 * single-thread decode cost per record (the same ``ImageInputFormat.read_record`` on the
-  same files, one process);
+  same files, one process); the native decoder's full cost and its entropy-only cost
+  (``jpeg_entropy_into``: what stays on the host in ``device`` mode), per record on one
+  thread and per 256-image batch on ``--decode-threads`` threads;
 * the GPU's idle share against the GPU-bound rate (``--gpu-rate``, the SPMD bench's
   records/s: ``1 - rate / gpu_rate``).
 
@@ -70,9 +75,10 @@ def main():
     ap.add_argument("--gpu-rate", type=float, default=0.0,
                     help="GPU-bound records/s (SPMD bench; 0: 77.5k ResNet-50, 84.5k Inception-v3)")
     ap.add_argument("--max-delay-ms", type=float, default=20.0)
-    ap.add_argument("--decode", default="staged", choices=["staged", "reader"],
+    ap.add_argument("--decode", default="staged", choices=["staged", "device", "reader"],
                     help="staged: the reader emits the JPEG bytes and the model's host stage decodes them with the "
-                         "native pool into the pinned slot (reader chained into the model worker); reader: Pillow "
+                         "native pool into the pinned slot (reader chained into the model worker); device: as staged, "
+                         "but the host only entropy-decodes and the GPU does the rest; reader: Pillow "
                          "decode in --readers reader processes (the reference's placement)")
     ap.add_argument("--decode-threads", type=int, default=32)
     ap.add_argument("--model", default="resnet50", choices=["resnet50", "inception_v3"],
@@ -130,6 +136,24 @@ def main():
                     nat.jpeg_decode_into(buf.ctypes.data + lo * rb, buf.nbytes - lo * rb, blobs[lo:lo + 64], rb,
                                          a.hw, a.hw, th)
             native_ms[th] = (time.perf_counter() - t0) / reps * 1e3
+        # the same for the entropy-only half (coefficient rows of 4:2:0 capacity, as the runner's)
+        import torch
+
+        stride, hbytes = nat.jpeg_coeff_layout(a.hw, a.hw, 420)
+        coef = torch.empty((256, stride), dtype=torch.uint8)
+        hdrs = torch.empty((256, hbytes), dtype=torch.uint8)
+        entropy_ms = {}
+        for th in (1, a.decode_threads):
+            st = nat.jpeg_entropy_into(coef.data_ptr(), coef.numel(), hdrs.data_ptr(), hdrs.numel(), blobs[:64], stride,
+                                       a.hw, a.hw, th)
+            assert not any(st), st
+            t0 = time.perf_counter()
+            reps = 2 if th == 1 else 10
+            for _ in range(reps):
+                for lo in range(0, 256, 64):
+                    nat.jpeg_entropy_into(coef[lo:].data_ptr(), coef[lo:].numel(), hdrs[lo:].data_ptr(),
+                                          hdrs[lo:].numel(), blobs[lo:lo + 64], stride, a.hw, a.hw, th)
+            entropy_ms[th] = (time.perf_counter() - t0) / reps * 1e3
 
         B = a.batch
         K = a.files // B - a.warmup - 1  # the last, partial batch is not timed
@@ -139,9 +163,10 @@ def main():
 
             extra["calibration_images"] = decode_jpegs(datas[:64], a.hw, a.hw)
         model = TimedModel(image_hw=(a.hw, a.hw), buckets=(B,), lanes=a.lanes or (3 if inc else 2), depth=3,
-                           lane_offset_us=1500.0, **extra).timed_window(a.warmup, K, out_dir)
+                           lane_offset_us=1500.0, jpeg_decode="device" if a.decode == "device" else "host",
+                           **extra).timed_window(a.warmup, K, out_dir)
         env = StreamExecutionEnvironment.get_execution_environment().set_parallelism(1)
-        staged = a.decode == "staged"
+        staged = a.decode in ("staged", "device")
         model.decode_threads = a.decode_threads
         fmt_job = ImageInputFormat(defer_decode=staged)
         if staged:  # one reader in the model's worker process (partitioned: the listing too)
@@ -162,8 +187,11 @@ def main():
         lat = np.asarray(r0["latencies_s"])
         print(json.dumps({
             "bench": "jpeg_e2e", "files": a.files, "hw": a.hw, "mean_jpeg_bytes": round(mean_bytes),
-            "decode": ("native baseline decoder on the model's host pool, into the pinned slot "
+            "decode": ("entropy decode on the model's host pool into pinned coefficient rows "
+                       f"({a.decode_threads} threads), IDCT / upsampling / colour on the GPU" if a.decode == "device"
+                       else "native baseline decoder on the model's host pool, into the pinned slot "
                        f"({a.decode_threads} threads)" if staged else f"Pillow in {a.readers} reader processes"),
+            "decode_mode": a.decode,
             "readers": 1 if staged else a.readers, "monitor": a.monitor if staged else "coordinator", "gpus": 1,
             "model": "Inception-v3 (fp8, compiled plan)" if inc else "ResNet-50 v1.5 (bf16, compiled plan)",
             "records_per_s": round(rate, 1), "job_records_per_s": round(a.files / wall, 1),
@@ -171,6 +199,8 @@ def main():
             "decode_ms_per_record_1thread": round(decode_ms, 3),
             "native_decode_ms_per_record_1thread": round(native_ms[1] / 256, 3),
             f"native_decode_ms_per_256_batch_{a.decode_threads}threads": round(native_ms[a.decode_threads], 3),
+            "entropy_only_ms_per_record_1thread": round(entropy_ms[1] / 256, 3),
+            f"entropy_only_ms_per_256_batch_{a.decode_threads}threads": round(entropy_ms[a.decode_threads], 3),
             "pillow_decode_bound_records_per_s": round(a.readers * 1e3 / decode_ms, 1),
             "gpu_rate_records_per_s": a.gpu_rate, "gpu_idle_share": round(max(0.0, 1 - rate / a.gpu_rate), 3),
             "p50_latency_ms": round(float(np.percentile(lat, 50)) * 1e3, 2) if lat.size else None,

@@ -139,6 +139,7 @@ def hip_flags() -> list[str]:
 def build_hip(force: bool = False, verbose: bool = False, jobs: int | None = None) -> Path:
     srcs = sorted(KERNELS.glob("*.hip"))
     hdrs = sorted(KERNELS.glob("*.h")) + sorted(KERNELS.glob("*.cuh"))
+    hdrs.append(CSRC / "jpeg_coeffs.h")  # the record kernels/jpeg.hip shares with csrc/jpeg.cpp
     flags = hip_flags()
     lib = hip_lib_path()
     dig = _digest(srcs + hdrs, flags)

@@ -57,6 +57,9 @@ class _Slot:
         # timeline mode: GPU timestamps of the first H2D piece and of the plan's first kernel
         self.t_h2d = torch.cuda.Event(enable_timing=True) if timing else None
         self.t_start = torch.cuda.Event(enable_timing=True) if timing else None
+        # JPEG coefficient rows and headers (``jpeg_decode="device"``): allocated by the runner
+        # on the slot's first JPEG batch in that mode
+        self.pinned_coef = self.pinned_hdr = self.dev_coef = self.dev_hdr = None
         self.busy = False
         self.n = 0
         self.ts = None
@@ -82,7 +85,8 @@ class PipelinedGpuRunner:
     def __init__(self, plans, feed: str, fetch_bufs: Callable[[Any], Sequence[torch.Tensor]],
                  record_shape, record_dtype=torch.uint8, depth: int = 3, device=None, gather_threads: int = 8,
                  stage_chunk: int = 64, lane_offset_us: float = 0.0, freeze_gc: bool = True, timeline: bool = False,
-                 interleave_head: bool = True, decode_threads: int | None = None, async_decode: bool = True):
+                 interleave_head: bool = True, decode_threads: int | None = None, async_decode: bool = True,
+                 jpeg_decode: str = "host"):
         lanes = plans if isinstance(plans, (list, tuple)) else [plans]
         self.lanes = [dict(sorted(p.items())) for p in lanes]
         self.plans = self.lanes[0]
@@ -113,6 +117,13 @@ class PipelinedGpuRunner:
         self.decode_threads = decode_threads
         self.decode_fallbacks = 0
         self.async_decode = async_decode
+        # "device": the host pool only entropy-decodes (Huffman) into pinned coefficient rows;
+        # dequantisation, IDCT, upsampling and colour conversion run on the GPU
+        # (kernels/jpeg.hip) into the staging slot.  What that path declines (progressive,
+        # 4:4:4 in a 4:2:0-sized row, another size, ...) is decoded on the host as in "host".
+        if jpeg_decode not in ("host", "device"):
+            raise ValueError(f"jpeg_decode is 'host' or 'device', not {jpeg_decode!r}")
+        self.jpeg_decode = jpeg_decode
         self._pending = None  # (DecodeJob, slot, bucket, payloads, ingest_ts, tags)
         self.stage_chunk = stage_chunk  # records per gather + H2D piece (0: whole batch at once)
         self.interleave_head = interleave_head  # launch each piece's head kernel inside the gather loop
@@ -187,8 +198,12 @@ class PipelinedGpuRunner:
         if self.async_decode and self._is_jpeg(payloads):
             b, slot, more = self._reserve(len(payloads))
             H, W, _ = self.record_shape
-            base, cap = slot.pinned_in.data_ptr(), slot.pinned_in.numel() * slot.pinned_in.element_size()
-            job = self._native.jpeg_decode_start(base, cap, payloads, self.record_bytes, H, W, self.decode_threads)
+            if self.jpeg_decode == "device":
+                job = self._native.jpeg_entropy_start(*self._coef_args(slot, 0), payloads, slot.pinned_coef.shape[1],
+                                                      H, W, self.decode_threads)
+            else:
+                base, cap = slot.pinned_in.data_ptr(), slot.pinned_in.numel() * slot.pinned_in.element_size()
+                job = self._native.jpeg_decode_start(base, cap, payloads, self.record_bytes, H, W, self.decode_threads)
             self._pending = (job, slot, b, payloads, ingest_ts, tags)
             return finished + more
         b, slot, more = self._reserve(len(payloads))
@@ -209,6 +224,10 @@ class PipelinedGpuRunner:
         st = job.wait()
         self.host_s["decode_wait"] = self.host_s.get("decode_wait", 0.0) + time.perf_counter() - t0
         bad = [k for k, code in enumerate(st) if code]
+        if self.jpeg_decode == "device":
+            self._decode_declined(slot, bad, payloads)
+            self._stage_launch(slot, b, payloads, ingest_ts, tags, decoded=True, declined=bad)
+            return []
         if bad:
             from ..graph.ops_io import fit_image_bytes
 
@@ -219,7 +238,8 @@ class PipelinedGpuRunner:
         self._stage_launch(slot, b, payloads, ingest_ts, tags, decoded=True)
         return []
 
-    def _stage_launch(self, slot: _Slot, b: int, payloads: list, ingest_ts, tags, decoded: bool) -> None:
+    def _stage_launch(self, slot: _Slot, b: int, payloads: list, ingest_ts, tags, decoded: bool,
+                      declined: Sequence[int] = ()) -> None:
         n = len(payloads)
         t1 = time.perf_counter()
         # host gather into the pinned slot in pieces, each piece's H2D issued as soon as it is
@@ -248,9 +268,20 @@ class PipelinedGpuRunner:
         if interleave:
             self._begin_lane(slot, lane, stream)
         jpeg = self._is_jpeg(payloads)
+        # device decode: a piece travels as coefficient rows + headers; the lane's stream turns
+        # them into the RGB rows of ``slot.dev_in`` (``spans[i]``: the piece's records, without
+        # the padding rows) before the piece's head kernel.  ``declined`` records are decoded
+        # on the host into their pinned RGB rows, and those rows alone are copied
+        dev_jpeg = jpeg and self.jpeg_decode == "device"
+        spans = list(pieces)
         with trace_range(f"gather[{n}/{b}]"):
             for i, (lo, hi) in enumerate(pieces):
-                if decoded:
+                if dev_jpeg:
+                    if decoded:
+                        host_rows = [k for k in declined if lo <= k < hi]
+                    else:
+                        host_rows = self._entropy_into(slot, lo, payloads[lo:hi])
+                elif decoded:
                     pass  # the rows are in the slot already (background decode)
                 elif jpeg:
                     self._decode_into(slot, base, cap, lo, payloads[lo:hi])
@@ -261,11 +292,22 @@ class PipelinedGpuRunner:
                     hi = b
                     pieces[i] = (lo, b)
                 with torch.cuda.stream(self.copy_stream):
-                    slot.dev_in[lo:hi].copy_(slot.pinned_in[lo:hi], non_blocking=True)
+                    if dev_jpeg:
+                        top = spans[i][1]
+                        slot.dev_coef[lo:top].copy_(slot.pinned_coef[lo:top], non_blocking=True)
+                        slot.dev_hdr[lo:top].copy_(slot.pinned_hdr[lo:top], non_blocking=True)
+                        for k in host_rows:
+                            slot.dev_in[k].copy_(slot.pinned_in[k], non_blocking=True)
+                        if hi > top:  # the zeroed padding rows
+                            slot.dev_in[top:hi].copy_(slot.pinned_in[top:hi], non_blocking=True)
+                    else:
+                        slot.dev_in[lo:hi].copy_(slot.pinned_in[lo:hi], non_blocking=True)
                     slot.h2d_parts[i].record(self.copy_stream)
                 if interleave:
                     with torch.cuda.stream(stream):
                         stream.wait_event(slot.h2d_parts[i])
+                        if dev_jpeg:
+                            self._idct_rgb(slot, *spans[i], stream)
                         plan.launch_head_piece(slot.dev_in, lo, hi)
         t2 = time.perf_counter()
         self._lane = (self._lane + 1) % len(self.lanes)
@@ -284,11 +326,19 @@ class PipelinedGpuRunner:
                     plan.replay_tail()
                 else:
                     chunked = getattr(plan, "replay_from_chunks", None)
+
+                    def wait_piece(i):
+                        stream.wait_event(slot.h2d_parts[i])
+                        if dev_jpeg:
+                            self._idct_rgb(slot, *spans[i], stream)
+
                     # head kernel per staged piece: the GPU starts on the first piece while
                     # the later ones are still in flight (shortens the pipeline fill)
                     if not (len(pieces) > 1 and chunked is not None and chunked(
-                            self.feed, slot.dev_in, pieces, lambda i: stream.wait_event(slot.h2d_parts[i]))):
+                            self.feed, slot.dev_in, pieces, wait_piece)):
                         stream.wait_event(slot.h2d)
+                        if dev_jpeg:
+                            self._idct_rgb(slot, 0, n, stream)
                         replay_from = getattr(plan, "replay_from", None)
                         if replay_from is not None:  # head kernel reads the staging slot: no D2D copy
                             replay_from(self.feed, slot.dev_in)
@@ -321,6 +371,52 @@ class PipelinedGpuRunner:
         rb = self.record_bytes
         self.decode_fallbacks += decode_jpegs_into(base + lo * rb, cap - lo * rb, blobs, rb, H, W,
                                                    self.decode_threads, rows=slot.pinned_in[lo:])
+
+    # ------------------------------------------------------------------ device JPEG decode
+    def _coef_args(self, slot: _Slot, lo: int) -> tuple[int, int, int, int]:
+        """(coefficient pointer, bytes, header pointer, bytes) of the slot's pinned rows from
+        record ``lo`` on, for the native entropy decoder; the slot's coefficient buffers
+        (pinned and device) are allocated here, on its first use in device mode.  A row has
+        4:2:0 capacity: the H2D volume of the RGB row it replaces."""
+        if slot.pinned_coef is None:
+            H, W, _ = self.record_shape
+            stride, hbytes = self._native.jpeg_coeff_layout(H, W, 420)
+            slot.pinned_coef = torch.empty((slot.bucket, stride), dtype=torch.uint8, pin_memory=True)
+            slot.pinned_hdr = torch.empty((slot.bucket, hbytes), dtype=torch.uint8, pin_memory=True)
+            slot.dev_coef = torch.empty((slot.bucket, stride), dtype=torch.uint8, device=self.device)
+            slot.dev_hdr = torch.empty((slot.bucket, hbytes), dtype=torch.uint8, device=self.device)
+        c, h = slot.pinned_coef[lo:], slot.pinned_hdr[lo:]
+        return c.data_ptr(), c.numel(), h.data_ptr(), h.numel()
+
+    def _entropy_into(self, slot: _Slot, lo: int, blobs: list) -> list[int]:
+        """JPEG byte strings -> coefficient rows and headers ``lo ..`` of the pinned slot (the
+        native entropy decoder on the host pool, GIL released).  Returns the records it
+        declined, which are decoded on the host into their pinned RGB rows instead."""
+        H, W, _ = self.record_shape
+        st = self._native.jpeg_entropy_into(*self._coef_args(slot, lo), blobs, slot.pinned_coef.shape[1], H, W,
+                                            self.decode_threads)
+        bad = [lo + k for k, code in enumerate(st) if code]
+        self._decode_declined(slot, bad, blobs, lo)
+        return bad
+
+    def _decode_declined(self, slot: _Slot, rows: list[int], blobs: list, lo: int = 0) -> None:
+        """The records the device path does not take, through the host path (the native
+        decoder, Pillow for what that declines too) into ``slot.pinned_in[k]``."""
+        from ..graph.ops_io import decode_jpegs_into
+
+        H, W, _ = self.record_shape
+        rb = self.record_bytes
+        base, cap = slot.pinned_in.data_ptr(), slot.pinned_in.numel() * slot.pinned_in.element_size()
+        for k in rows:
+            decode_jpegs_into(base + k * rb, cap - k * rb, [blobs[k - lo]], rb, H, W, 1, rows=slot.pinned_in[k:])
+        self.decode_fallbacks += len(rows)
+
+    def _idct_rgb(self, slot: _Slot, lo: int, hi: int, stream) -> None:
+        from ..ops import kernels as K
+
+        H, W, _ = self.record_shape
+        K.jpeg_idct_rgb(slot.dev_coef[lo:hi], slot.dev_hdr[lo:hi], slot.dev_in[lo:hi], hi - lo, H, W,
+                        stream.cuda_stream)
 
     def _begin_lane(self, slot: _Slot, lane: int, stream) -> None:
         """The lane's stream work that precedes a batch: the phase delay of a restarting

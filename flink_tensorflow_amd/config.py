@@ -66,6 +66,10 @@ class EngineConfig:
     # "allgather" = the padded all-gather of one row per lookup (capturable, most bytes)
     wd_sparse_exchange: str = "owner"
     wd_bucket_slack: float = 2.0       # bucket capacity = slack x (slots / world) + 64
+    # JPEG records of the image models: "host" = the native decoder writes RGB into the pinned
+    # slot; "device" = the host only entropy-decodes, the IDCT / upsampling / colour
+    # conversion run on the GPU (kernels/jpeg.hip).  A model's jpeg_decode= overrides it
+    jpeg_decode: str = "host"
     extra: dict = field(default_factory=dict)
 
     # ------------------------------------------------------------------ sources
@@ -152,6 +156,8 @@ class EngineConfig:
             raise ValueError("arena_fraction must be in (0, 1]")
         if self.wd_sparse_exchange not in ("bucketed", "owner", "allgather"):
             raise ValueError("wd_sparse_exchange must be bucketed, owner or allgather")
+        if self.jpeg_decode not in ("host", "device"):
+            raise ValueError("jpeg_decode must be host or device")
         if self.wd_bucket_slack <= 0:
             raise ValueError("wd_bucket_slack must be positive")
         if self.batch_buckets and sorted(self.batch_buckets) != list(self.batch_buckets):

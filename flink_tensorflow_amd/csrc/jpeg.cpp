@@ -13,6 +13,11 @@
 // with the triangle filter ("fancy" upsampling).  Progressive / arithmetic / 12-bit
 // files and images of another size than the slot's are reported back (status per image)
 // and the caller decodes those with Pillow.
+//
+// The decode also comes in two halves (jpeg_entropy_into, jpeg_coeffs_to_rgb): the entropy
+// decoder alone, writing quantised coefficients and a header per image (jpeg_coeffs.h), and
+// the arithmetic that follows it, which the GPU runs instead (kernels/jpeg.hip) when the
+// runner is asked to (batching/engine.py jpeg_decode="device").
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -27,6 +32,7 @@
 #include <thread>
 #include <vector>
 
+#include "jpeg_coeffs.h"
 #include "native.h"
 
 namespace {
@@ -36,7 +42,9 @@ constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25,
                                  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
                                  58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-enum Status : int { kOk = 0, kNotJpeg = 1, kUnsupported = 2, kCorrupt = 3, kSize = 4 };
+// kSlot: a file the host decoder takes but the coefficient path does not (sampling other
+// than 4:4:4 / 4:2:2 / 4:2:0, or more samples than the caller's row holds)
+enum Status : int { kOk = 0, kNotJpeg = 1, kUnsupported = 2, kCorrupt = 3, kSize = 4, kSlot = 5 };
 
 struct Huff {
   // canonical table: lookup of the first 9 bits, then the classic maxcode walk
@@ -204,12 +212,15 @@ static inline void pass8(__m256* v) {
   const __m256 q1 = _mm256_add_ps(o0, o3), q2 = _mm256_add_ps(o1, o2);
   const __m256 q3 = _mm256_add_ps(o0, o2), q4 = _mm256_add_ps(o1, o3);
   const __m256 q5 = _mm256_mul_ps(_mm256_add_ps(q3, q4), k(1.175875602f));
-  const __m256 r1 = _mm256_mul_ps(q1, k(-0.899976223f)), r2 = _mm256_mul_ps(q2, k(-2.562915447f));
+  const __m256 k1 = k(-0.899976223f), k2 = k(-2.562915447f);
   const __m256 r3 = _mm256_fmadd_ps(q3, k(-1.961570560f), q5), r4 = _mm256_fmadd_ps(q4, k(-0.390180644f), q5);
-  o0 = _mm256_fmadd_ps(o0, k(0.298631336f), _mm256_add_ps(r1, r3));
-  o1 = _mm256_fmadd_ps(o1, k(2.053119869f), _mm256_add_ps(r2, r4));
-  o2 = _mm256_fmadd_ps(o2, k(3.072711026f), _mm256_add_ps(r2, r3));
-  o3 = _mm256_fmadd_ps(o3, k(1.501321110f), _mm256_add_ps(r1, r4));
+  // q1 * k1 + r3 and its like as FMAs: what the compiler's default contraction made of
+  // mul + add here anyway, spelled out so that the results do not hang on that default and
+  // the scalar and device back halves (idct_exact, kernels/jpeg.hip) can mirror the source
+  o0 = _mm256_fmadd_ps(o0, k(0.298631336f), _mm256_fmadd_ps(q1, k1, r3));
+  o1 = _mm256_fmadd_ps(o1, k(2.053119869f), _mm256_fmadd_ps(q2, k2, r4));
+  o2 = _mm256_fmadd_ps(o2, k(3.072711026f), _mm256_fmadd_ps(q2, k2, r3));
+  o3 = _mm256_fmadd_ps(o3, k(1.501321110f), _mm256_fmadd_ps(q1, k1, r4));
   v[0] = _mm256_add_ps(t10, o3);
   v[7] = _mm256_sub_ps(t10, o3);
   v[1] = _mm256_add_ps(t11, o2);
@@ -254,6 +265,17 @@ class Decoder {
  public:
   Decoder(const uint8_t* data, size_t n) : p_(data), end_(data + n) {}
 
+  // Entropy decoding only: the quantised coefficients go to `row` (`cap` int16 elements,
+  // layout of jpeg_coeffs.h) and the geometry and tables to `hdr`, for the back half to run
+  // elsewhere (jpeg_coeffs_to_rgb, kernels/jpeg.hip); returns a Status (hdr->status is the
+  // caller's to set)
+  int entropy(int16_t* row, size_t cap, JpegCoeffHeader* hdr, int want_h, int want_w) {
+    coef_ = row;
+    coef_cap_ = cap;
+    hdr_ = hdr;
+    return decode(nullptr, want_h, want_w);
+  }
+
   // decodes into dst (H x W x 3, row stride W*3); returns a Status
   int decode(uint8_t* dst, int want_h, int want_w) {
     if (end_ - p_ < 4 || p_[0] != 0xFF || p_[1] != 0xD8) return kNotJpeg;
@@ -290,10 +312,11 @@ class Decoder {
           if (!frame) return kCorrupt;
           st = sos(seg, seg_end);
           if (st != kOk) return st;
+          if (coef_ && (st = coef_frame()) != kOk) return st;
           p_ = seg_end;
           st = scan();
           if (st != kOk) return st;
-          return convert(dst);  // one interleaved scan carries every component (baseline)
+          return coef_ ? kOk : convert(dst);  // one interleaved scan carries every component (baseline)
         }
         default: break;  // APPn, COM, ...
       }
@@ -309,6 +332,7 @@ class Decoder {
       const int pq = s[0] >> 4, tq = s[0] & 15;
       ++s;
       if (tq > 3 || s + (pq ? 128 : 64) > e) return kCorrupt;
+      qt16_[tq] = pq != 0;
       for (int k = 0; k < 64; ++k) {
         qt_[tq][k] = pq ? ((s[2 * k] << 8) | s[2 * k + 1]) : s[k];
       }
@@ -347,7 +371,7 @@ class Decoder {
       mcuy_ = (h_ + 7) / 8;
       c_[0].bw = mcux_;
       c_[0].bh = mcuy_;
-      c_[0].plane.assign(size_t(c_[0].bw) * 8 * c_[0].bh * 8, 0);
+      if (!coef_) c_[0].plane.assign(size_t(c_[0].bw) * 8 * c_[0].bh * 8, 0);
       return kOk;
     }
     hmax_ = vmax_ = 1;
@@ -367,7 +391,7 @@ class Decoder {
       Component& c = c_[i];
       c.bw = mcux_ * c.h;
       c.bh = mcuy_ * c.v;
-      c.plane.assign(size_t(c.bw) * 8 * c.bh * 8, 0);
+      if (!coef_) c.plane.assign(size_t(c.bw) * 8 * c.bh * 8, 0);
     }
     return kOk;
   }
@@ -383,6 +407,28 @@ class Decoder {
       c->td = s[2 + 2 * i] >> 4;
       c->ta = s[2 + 2 * i] & 15;
       if (c->td > 3 || c->ta > 3 || !dc_[c->td].ok || !ac_[c->ta].ok) return kCorrupt;
+    }
+    return kOk;
+  }
+
+  // coefficient mode, once the frame and scan headers are in: what the back half takes
+  // (8-bit tables, grayscale or chroma 1x1 under luma 1x1 / 2x1 / 2x2, a row that holds
+  // every block), the planes' places in the row and the header record
+  int coef_frame() {
+    if (nc_ == 3) {
+      const bool luma_ok = (c_[0].h == 1 && c_[0].v == 1) || (c_[0].h == 2 && c_[0].v <= 2);
+      if (!luma_ok || c_[1].h != 1 || c_[1].v != 1 || c_[2].h != 1 || c_[2].v != 1) return kSlot;
+    }
+    size_t off = 0;
+    hdr_->ncomp = nc_;
+    for (int i = 0; i < nc_; ++i) {
+      const Component& c = c_[i];
+      if (qt16_[c.tq]) return kUnsupported;
+      hdr_->comp[i] = {c.h, c.v, c.bw, c.bh, int32_t(off)};
+      std::memcpy(hdr_->qt[i], qt_[c.tq], sizeof(hdr_->qt[i]));
+      coef_off_[i] = off;
+      off += size_t(c.bw) * c.bh * 64;
+      if (off > coef_cap_) return kSlot;
     }
     return kOk;
   }
@@ -457,6 +503,9 @@ class Decoder {
     nbits_ -= len;
     return h.vals[h.valoff[len] + code];
   }
+  // DEQ: F holds the dequantised coefficients (the host IDCT's input), else the quantised
+  // ones as coded
+  template <bool DEQ>
   bool block(Component& c, int32_t* F, bool& any_ac) {
     std::memset(F, 0, 64 * sizeof(int32_t));
     any_ac = false;
@@ -465,7 +514,7 @@ class Decoder {
     const int t = huff(dc_[c.td]);
     if (t < 0 || t > 11) return false;
     c.pred += t ? extend(getbits(t), t) : 0;
-    F[0] = c.pred * q[0];
+    F[0] = c.pred * (DEQ ? q[0] : 1);
     const Huff& ac = ac_[c.ta];
     for (int k = 1; k < 64;) {
       refill();
@@ -473,7 +522,7 @@ class Decoder {
       if (const int fl = ac.fast_len[p9]) {  // code + magnitude in the first 9 bits
         k += ac.fast_run[p9];
         if (k > 63) return false;
-        F[kZigzag[k]] = ac.fast_val[p9] * q[k];
+        F[kZigzag[k]] = ac.fast_val[p9] * (DEQ ? q[k] : 1);
         any_ac = true;
         ++k;
         bitbuf_ <<= fl;
@@ -486,7 +535,7 @@ class Decoder {
       if (s) {
         k += r;
         if (k > 63) return false;
-        F[kZigzag[k]] = extend(getbits(s), s) * q[k];
+        F[kZigzag[k]] = extend(getbits(s), s) * (DEQ ? q[k] : 1);
         any_ac = true;
         ++k;
       } else if (r == 15) {
@@ -525,7 +574,14 @@ class Decoder {
           for (int by = 0; by < c.v; ++by)
             for (int bx = 0; bx < c.h; ++bx) {
               bool any_ac;
-              if (!block(c, F, any_ac)) return kCorrupt;
+              if (coef_) {  // every block is written in full; AC magnitudes have <= 15 bits
+                if (!block<false>(c, F, any_ac)) return kCorrupt;
+                if (c.pred < -32768 || c.pred > 32767) return kUnsupported;
+                int16_t* o = coef_ + coef_off_[i] + (size_t(my * c.v + by) * c.bw + (mx * c.h + bx)) * 64;
+                for (int k = 0; k < 64; ++k) o[k] = int16_t(F[k]);
+                continue;
+              }
+              if (!block<true>(c, F, any_ac)) return kCorrupt;
               const int row = (my * c.v + by) * 8, col = (mx * c.h + bx) * 8;
               id.run(F, c.plane.data() + size_t(row) * stride + col, stride, any_ac);
             }
@@ -675,6 +731,10 @@ class Decoder {
   const uint8_t* p_;
   const uint8_t* end_;
   uint16_t qt_[4][64] = {};
+  bool qt16_[4] = {};  // the table came with 16-bit entries (Pq = 1)
+  int16_t* coef_ = nullptr;  // coefficient mode (entropy()): the row, its capacity, the header
+  size_t coef_cap_ = 0, coef_off_[3] = {};
+  JpegCoeffHeader* hdr_ = nullptr;
   Huff dc_[4], ac_[4];
   Component c_[3];
   int h_ = 0, w_ = 0, nc_ = 0, hmax_ = 1, vmax_ = 1, mcux_ = 0, mcuy_ = 0, restart_ = 0;
@@ -683,12 +743,11 @@ class Decoder {
   bool marker_ = false;
 };
 
-// images[i] -> dst + i * stride (H x W x 3 uint8); per-image Status
-std::vector<int> jpeg_decode_into(uintptr_t dst, size_t dst_bytes, const py::list& images, size_t stride, int H, int W,
-                                  int nthreads) {
+// status[i] = fn(i, bytes of images[i], their length) on the host pool, GIL released; a
+// throwing fn counts as corrupt
+template <class Fn>
+std::vector<int> run_images(const py::list& images, int nthreads, const Fn& fn) {
   const size_t n = images.size();
-  if (size_t(H) * W * 3 > stride) throw std::invalid_argument("jpeg_decode_into: stride smaller than H*W*3");
-  if (n * stride > dst_bytes) throw std::invalid_argument("jpeg_decode_into: slot too small for the batch");
   std::vector<Py_buffer> views(n);
   size_t held = 0;
   struct Release {
@@ -703,19 +762,64 @@ std::vector<int> jpeg_decode_into(uintptr_t dst, size_t dst_bytes, const py::lis
     ++held;
   }
   std::vector<int> status(n, kOk);
-  uint8_t* d = reinterpret_cast<uint8_t*>(dst);
   {
     py::gil_scoped_release nogil;
     pool_run(int(n), std::max(1, nthreads), [&](int i) {
-      Decoder dec(static_cast<const uint8_t*>(views[i].buf), size_t(views[i].len));
       try {
-        status[i] = dec.decode(d + size_t(i) * stride, H, W);
+        status[i] = fn(i, static_cast<const uint8_t*>(views[i].buf), size_t(views[i].len));
       } catch (...) {
         status[i] = kCorrupt;
       }
     });
   }
   return status;
+}
+
+// images[i] -> dst + i * stride (H x W x 3 uint8); per-image Status
+std::vector<int> jpeg_decode_into(uintptr_t dst, size_t dst_bytes, const py::list& images, size_t stride, int H, int W,
+                                  int nthreads) {
+  const size_t n = images.size();
+  if (size_t(H) * W * 3 > stride) throw std::invalid_argument("jpeg_decode_into: stride smaller than H*W*3");
+  if (n * stride > dst_bytes) throw std::invalid_argument("jpeg_decode_into: slot too small for the batch");
+  uint8_t* d = reinterpret_cast<uint8_t*>(dst);
+  return run_images(images, nthreads, [=](int i, const uint8_t* data, size_t len) {
+    return Decoder(data, len).decode(d + size_t(i) * stride, H, W);
+  });
+}
+
+// where the coefficient rows and headers of a batch go, checked against the caller's buffers
+struct CoeffRows {
+  int16_t* coef;
+  JpegCoeffHeader* hdr;
+  size_t stride;  // bytes per coefficient row
+
+  CoeffRows(const char* who, uintptr_t coef_ptr, size_t coef_bytes, uintptr_t hdr_ptr, size_t hdr_bytes, size_t n,
+            size_t stride_bytes)
+      : coef(reinterpret_cast<int16_t*>(coef_ptr)), hdr(reinterpret_cast<JpegCoeffHeader*>(hdr_ptr)),
+        stride(stride_bytes) {
+    const std::string w(who);
+    if (stride % 16 || coef_ptr % 16) throw std::invalid_argument(w + ": coefficient rows must be 16-byte aligned");
+    if (hdr_ptr % alignof(JpegCoeffHeader)) throw std::invalid_argument(w + ": headers must be 16-byte aligned");
+    if (n * stride > coef_bytes) throw std::invalid_argument(w + ": coefficient buffer too small for the batch");
+    if (n * sizeof(JpegCoeffHeader) > hdr_bytes) throw std::invalid_argument(w + ": header buffer too small for the batch");
+  }
+  int16_t* row(int i) const { return coef + size_t(i) * (stride / 2); }
+  int entropy(int i, const uint8_t* data, size_t len, int H, int W) const {
+    JpegCoeffHeader* h = hdr + i;
+    std::memset(h, 0, sizeof(*h));
+    h->status = kCorrupt;  // should the decoder throw
+    const int st = Decoder(data, len).entropy(row(i), stride / 2, h, H, W);
+    h->status = st;
+    return st;
+  }
+};
+
+// images[i] -> coefficient row i and header i (jpeg_coeffs.h); per-image Status, also in the header
+std::vector<int> jpeg_entropy_into(uintptr_t coef, size_t coef_bytes, uintptr_t hdr, size_t hdr_bytes,
+                                   const py::list& images, size_t stride, int H, int W, int nthreads) {
+  const CoeffRows rows("jpeg_entropy_into", coef, coef_bytes, hdr, hdr_bytes, images.size(), stride);
+  return run_images(images, nthreads,
+                    [=](int i, const uint8_t* data, size_t len) { return rows.entropy(i, data, len, H, W); });
 }
 
 // A decode running in the background (jpeg_decode_start): a host thread drives the pool
@@ -750,11 +854,10 @@ struct DecodeJob {
   }
 };
 
-std::shared_ptr<DecodeJob> jpeg_decode_start(uintptr_t dst, size_t dst_bytes, const py::list& images, size_t stride,
-                                             int H, int W, int nthreads) {
+// run_images in the background: fn is copied into the job's thread
+template <class Fn>
+std::shared_ptr<DecodeJob> start_images(const py::list& images, int nthreads, const Fn& fn) {
   const size_t n = images.size();
-  if (size_t(H) * W * 3 > stride) throw std::invalid_argument("jpeg_decode_start: stride smaller than H*W*3");
-  if (n * stride > dst_bytes) throw std::invalid_argument("jpeg_decode_start: slot too small for the batch");
   auto job = std::make_shared<DecodeJob>();
   job->keep = images;
   job->views.resize(n);
@@ -764,12 +867,10 @@ std::shared_ptr<DecodeJob> jpeg_decode_start(uintptr_t dst, size_t dst_bytes, co
   }
   job->status.assign(n, kOk);
   DecodeJob* j = job.get();
-  uint8_t* d = reinterpret_cast<uint8_t*>(dst);
-  job->th = std::thread([j, d, stride, H, W, nthreads, n]() {
+  job->th = std::thread([j, fn, nthreads, n]() {
     pool_run(int(n), std::max(1, nthreads), [&](int i) {
-      Decoder dec(static_cast<const uint8_t*>(j->views[i].buf), size_t(j->views[i].len));
       try {
-        j->status[i] = dec.decode(d + size_t(i) * stride, H, W);
+        j->status[i] = fn(i, static_cast<const uint8_t*>(j->views[i].buf), size_t(j->views[i].len));
       } catch (...) {
         j->status[i] = kCorrupt;
       }
@@ -777,6 +878,187 @@ std::shared_ptr<DecodeJob> jpeg_decode_start(uintptr_t dst, size_t dst_bytes, co
     j->finished.store(true, std::memory_order_release);
   });
   return job;
+}
+
+std::shared_ptr<DecodeJob> jpeg_decode_start(uintptr_t dst, size_t dst_bytes, const py::list& images, size_t stride,
+                                             int H, int W, int nthreads) {
+  const size_t n = images.size();
+  if (size_t(H) * W * 3 > stride) throw std::invalid_argument("jpeg_decode_start: stride smaller than H*W*3");
+  if (n * stride > dst_bytes) throw std::invalid_argument("jpeg_decode_start: slot too small for the batch");
+  uint8_t* d = reinterpret_cast<uint8_t*>(dst);
+  return start_images(images, nthreads, [=](int i, const uint8_t* data, size_t len) {
+    return Decoder(data, len).decode(d + size_t(i) * stride, H, W);
+  });
+}
+
+std::shared_ptr<DecodeJob> jpeg_entropy_start(uintptr_t coef, size_t coef_bytes, uintptr_t hdr, size_t hdr_bytes,
+                                              const py::list& images, size_t stride, int H, int W, int nthreads) {
+  const CoeffRows rows("jpeg_entropy_start", coef, coef_bytes, hdr, hdr_bytes, images.size(), stride);
+  return start_images(images, nthreads,
+                      [=](int i, const uint8_t* data, size_t len) { return rows.entropy(i, data, len, H, W); });
+}
+
+// (coefficient row stride in bytes, header bytes) of an H x W slot that holds every
+// supported file up to `max_sampling`: 420 (the default capacity, 1.5 samples per pixel of
+// the 16-padded image: the H2D volume of the RGB row), 422 or 444
+py::tuple jpeg_coeff_layout(int H, int W, int max_sampling) {
+  if (H <= 0 || W <= 0) throw std::invalid_argument("jpeg_coeff_layout: bad size");
+  const auto pad = [](int v, int m) { return size_t((v + m - 1) / m) * m; };
+  size_t samples = std::max(pad(H, 8) * pad(W, 8), pad(H, 16) * pad(W, 16) * 3 / 2);  // grayscale, 4:2:0
+  if (max_sampling == 422 || max_sampling == 444) samples = std::max(samples, pad(H, 8) * pad(W, 16) * 2);
+  if (max_sampling == 444) samples = std::max(samples, pad(H, 8) * pad(W, 8) * 3);
+  if (max_sampling != 420 && max_sampling != 422 && max_sampling != 444)
+    throw std::invalid_argument("jpeg_coeff_layout: max_sampling is 420, 422 or 444");
+  return py::make_tuple(samples * sizeof(int16_t), sizeof(JpegCoeffHeader));
+}
+
+// ---- the back half on the host: dequantisation, IDCT, upsampling and colour conversion of
+// coefficient rows, in scalar code whose every operation is the one Idct::run_avx2 /
+// Decoder::upsample / Decoder::convert's scalar loop perform (an FMA where pass8 has one, a
+// separately rounded multiply or add where it has one), so that the device kernel
+// (kernels/jpeg.hip), which mirrors this, can be checked against jpeg_decode_into without a
+// GPU.  The compiler must not fuse what is written apart here.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+
+inline void pass_exact(float* v) {
+  const float z1 = (v[2] + v[6]) * 0.541196100f;
+  const float t2 = std::fmaf(-v[6], 1.847759065f, z1);
+  const float t3 = std::fmaf(v[2], 0.765366865f, z1);
+  const float t0 = v[0] + v[4], t1 = v[0] - v[4];
+  const float t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  float o0 = v[7], o1 = v[5], o2 = v[3], o3 = v[1];
+  const float q1 = o0 + o3, q2 = o1 + o2, q3 = o0 + o2, q4 = o1 + o3;
+  const float q5 = (q3 + q4) * 1.175875602f;
+  const float k1 = -0.899976223f, k2 = -2.562915447f;
+  const float r3 = std::fmaf(q3, -1.961570560f, q5), r4 = std::fmaf(q4, -0.390180644f, q5);
+  o0 = std::fmaf(o0, 0.298631336f, std::fmaf(q1, k1, r3));
+  o1 = std::fmaf(o1, 2.053119869f, std::fmaf(q2, k2, r4));
+  o2 = std::fmaf(o2, 3.072711026f, std::fmaf(q2, k2, r3));
+  o3 = std::fmaf(o3, 1.501321110f, std::fmaf(q1, k1, r4));
+  v[0] = t10 + o3;
+  v[7] = t10 - o3;
+  v[1] = t11 + o2;
+  v[6] = t11 - o2;
+  v[2] = t12 + o1;
+  v[5] = t12 - o1;
+  v[3] = t13 + o0;
+  v[4] = t13 - o0;
+}
+
+// one block: c (64 int16, natural order) x q (natural order) -> 8 x 8 samples at out
+void idct_exact(const int16_t* c, const uint16_t* q, uint8_t* out, int stride) {
+  float g[8][8];
+  for (int u = 0; u < 8; ++u) {  // rows: over the horizontal frequencies of row u
+    float v[8];
+    for (int k = 0; k < 8; ++k) v[k] = float(int32_t(c[8 * u + k]) * int32_t(q[8 * u + k]));
+    pass_exact(v);
+    for (int y = 0; y < 8; ++y) g[u][y] = v[y];
+  }
+  for (int y = 0; y < 8; ++y) {  // columns
+    float v[8];
+    for (int u = 0; u < 8; ++u) v[u] = g[u][y];
+    pass_exact(v);
+    for (int x = 0; x < 8; ++x) {
+      const int i = int(std::fmaf(v[x], 0.125f, 128.5f));
+      out[x * stride + y] = uint8_t(i < 0 ? 0 : i > 255 ? 255 : i);
+    }
+  }
+}
+
+#pragma GCC pop_options
+
+// chroma sample of the full-resolution pixel (y, x): the triangle filter of
+// Decoder::upsample on plane p (row pitch cw), vw x vh valid samples
+inline int upsample_at(const uint8_t* p, int cw, int vw, int vh, int sx, int sy, int y, int x) {
+  const uint8_t *r0, *r1;
+  int wv;
+  if (sy == 2) {
+    const int yc = y >> 1;
+    const int yf = (y & 1) ? (yc + 1 < vh ? yc + 1 : yc) : (yc > 0 ? yc - 1 : 0);
+    r0 = p + size_t(yc) * cw;
+    r1 = p + size_t(yf) * cw;
+    wv = 3;
+  } else {
+    r0 = r1 = p + size_t(y) * cw;
+    wv = 4;
+  }
+  const auto cs = [&](int j) { return wv * r0[j] + (4 - wv) * r1[j]; };
+  if (sx != 2) return (cs(x) + 2) >> 2;
+  const int xc = x >> 1;
+  const int xn = (x & 1) ? (xc + 1 < vw ? xc + 1 : xc) : (xc > 0 ? xc - 1 : 0);
+  return (3 * cs(xc) + cs(xn) + 8) >> 4;
+}
+
+int coeffs_to_rgb_one(const int16_t* row, size_t cap, const JpegCoeffHeader& h, uint8_t* dst, int H, int W) {
+  if (h.status != kOk) return h.status;
+  const int nc = h.ncomp;
+  if (nc != 1 && nc != 3) return kCorrupt;
+  const int hmax = h.comp[0].h, vmax = h.comp[0].v;
+  std::vector<uint8_t> plane[3];
+  for (int i = 0; i < nc; ++i) {
+    const JpegCoeffComponent& c = h.comp[i];
+    if (c.h < 1 || c.h > hmax || c.v < 1 || c.v > vmax || hmax > 2 || vmax > 2 || c.bw <= 0 || c.bh <= 0 ||
+        c.offset < 0 || size_t(c.offset) + size_t(c.bw) * c.bh * 64 > cap ||
+        size_t(c.bw) * 8 * (hmax / c.h) < size_t(W) ||
+        size_t(c.bh) * 8 * (vmax / c.v) < size_t(H))
+      return kCorrupt;
+    uint16_t q[64];
+    for (int k = 0; k < 64; ++k) q[kZigzag[k]] = h.qt[i][k];
+    const int cw = c.bw * 8;
+    plane[i].resize(size_t(cw) * c.bh * 8);
+    for (int by = 0; by < c.bh; ++by)
+      for (int bx = 0; bx < c.bw; ++bx)
+        idct_exact(row + c.offset + (size_t(by) * c.bw + bx) * 64, q, plane[i].data() + size_t(by) * 8 * cw + bx * 8, cw);
+  }
+  for (int y = 0; y < H; ++y) {
+    uint8_t* d = dst + size_t(y) * W * 3;
+    const uint8_t* ys = plane[0].data() + size_t(y) * h.comp[0].bw * 8;
+    if (nc == 1) {
+      for (int x = 0; x < W; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = ys[x];
+      continue;
+    }
+    for (int x = 0; x < W; ++x) {
+      int cc[2];
+      for (int i = 1; i < 3; ++i) {
+        const JpegCoeffComponent& c = h.comp[i];
+        const int sx = hmax / c.h, sy = vmax / c.v;
+        cc[i - 1] = (sx == 1 && sy == 1) ? plane[i][size_t(y) * c.bw * 8 + x]
+                                         : upsample_at(plane[i].data(), c.bw * 8, (W + sx - 1) / sx, (H + sy - 1) / sy,
+                                                       sx, sy, y, x);
+      }
+      const int Y = ys[x] << 16, B = cc[0] - 128, R = cc[1] - 128;  // JFIF YCbCr -> RGB in 16.16 fixed point
+      const int r = (Y + 91881 * R + 32768) >> 16;
+      const int g = (Y - 22554 * B - 46802 * R + 32768) >> 16;
+      const int b = (Y + 116130 * B + 32768) >> 16;
+      d[3 * x] = uint8_t(r < 0 ? 0 : r > 255 ? 255 : r);
+      d[3 * x + 1] = uint8_t(g < 0 ? 0 : g > 255 ? 255 : g);
+      d[3 * x + 2] = uint8_t(b < 0 ? 0 : b > 255 ? 255 : b);
+    }
+  }
+  return kOk;
+}
+
+// coefficient rows + headers -> RGB rows at dst + i * dst_stride, on the host pool; rows
+// whose header status is non-zero are left alone.  Returns the headers' statuses.
+std::vector<int> jpeg_coeffs_to_rgb(uintptr_t coef, size_t coef_bytes, uintptr_t hdr, size_t hdr_bytes, uintptr_t dst,
+                                    size_t dst_bytes, int n, size_t stride, size_t dst_stride, int H, int W,
+                                    int nthreads) {
+  if (n < 0 || H <= 0 || W <= 0) throw std::invalid_argument("jpeg_coeffs_to_rgb: bad shape");
+  const CoeffRows rows("jpeg_coeffs_to_rgb", coef, coef_bytes, hdr, hdr_bytes, size_t(n), stride);
+  if (size_t(H) * W * 3 > dst_stride) throw std::invalid_argument("jpeg_coeffs_to_rgb: dst_stride smaller than H*W*3");
+  if (size_t(n) * dst_stride > dst_bytes) throw std::invalid_argument("jpeg_coeffs_to_rgb: dst too small for the batch");
+  std::vector<int> status(size_t(n), kOk);
+  uint8_t* d = reinterpret_cast<uint8_t*>(dst);
+  py::gil_scoped_release nogil;
+  pool_run(n, std::max(1, nthreads), [&](int i) {
+    try {
+      status[i] = coeffs_to_rgb_one(rows.row(i), stride / 2, rows.hdr[i], d + size_t(i) * dst_stride, H, W);
+    } catch (...) {
+      status[i] = kCorrupt;
+    }
+  });
+  return status;
 }
 
 // (height, width, components, baseline) from the frame header, or (0, 0, 0, false) when
@@ -861,6 +1143,25 @@ void register_jpeg(py::module_& m) {
   m.def("jpeg_decode_start", &jpeg_decode_start, py::arg("dst"), py::arg("dst_bytes"), py::arg("images"),
         py::arg("stride"), py::arg("h"), py::arg("w"), py::arg("nthreads") = 8,
         "jpeg_decode_into in the background: returns a DecodeJob (done() / wait() -> statuses).");
+  m.def("jpeg_entropy_into", &jpeg_entropy_into, py::arg("coef"), py::arg("coef_bytes"), py::arg("headers"),
+        py::arg("header_bytes"), py::arg("images"), py::arg("stride"), py::arg("h"), py::arg("w"),
+        py::arg("nthreads") = 8,
+        "Entropy-decodes baseline JPEG byte strings: image i's quantised coefficients (int16, de-zigzagged, component "
+        "planes of MCU-padded blocks) go to the `stride`-byte row i at `coef` and its geometry, tables and status to "
+        "the fixed-size header i at `headers`.  Statuses as jpeg_decode_into, plus 5: a file the host decoder takes "
+        "but not this row (sampling other than 4:4:4 / 4:2:2 / 4:2:0, or more samples than the row holds).");
+  m.def("jpeg_entropy_start", &jpeg_entropy_start, py::arg("coef"), py::arg("coef_bytes"), py::arg("headers"),
+        py::arg("header_bytes"), py::arg("images"), py::arg("stride"), py::arg("h"), py::arg("w"),
+        py::arg("nthreads") = 8, "jpeg_entropy_into in the background: returns a DecodeJob.");
+  m.def("jpeg_coeff_layout", &jpeg_coeff_layout, py::arg("h"), py::arg("w"), py::arg("max_sampling") = 420,
+        "(coefficient row stride in bytes, header bytes) of an h x w slot taking files up to 4:2:0 (420), 4:2:2 "
+        "(422) or 4:4:4 (444).");
+  m.def("jpeg_coeffs_to_rgb", &jpeg_coeffs_to_rgb, py::arg("coef"), py::arg("coef_bytes"), py::arg("headers"),
+        py::arg("header_bytes"), py::arg("dst"), py::arg("dst_bytes"), py::arg("n"), py::arg("stride"),
+        py::arg("dst_stride"), py::arg("h"), py::arg("w"), py::arg("nthreads") = 8,
+        "The back half of the decode on the host pool: coefficient rows + headers -> RGB rows (H x W x 3) of "
+        "`dst_stride` bytes at `dst`, in the arithmetic of jpeg_decode_into's IDCT, upsampling and scalar colour "
+        "conversion; rows whose header status is non-zero are left alone.  Returns the statuses.");
   m.def("read_files", &read_files, py::arg("paths"), py::arg("nthreads") = 8,
         "Reads whole files on the host pool (GIL released); bytes per path, None for a file that cannot be read.");
   m.def("jpeg_decode_into", &jpeg_decode_into, py::arg("dst"), py::arg("dst_bytes"), py::arg("images"),

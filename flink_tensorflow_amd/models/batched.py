@@ -43,8 +43,12 @@ class SignatureBatchedModel(SavedModel_, BatchedGpuModel):
                  input_key: str | None = None, output_keys: Sequence[str] | None = None,
                  record_shape: Sequence[int] | None = None, buckets: Sequence[int] = (64, 256), lanes: int = 2,
                  depth: int = 3, precision: str = "bf16", tags: Sequence[str] = (TAG_SERVE,), device=None,
-                 distributed_weights: bool = False, pack_tokens: bool | None = None, lane_offset_us: float = 0.0):
+                 distributed_weights: bool = False, pack_tokens: bool | None = None, lane_offset_us: float = 0.0,
+                 jpeg_decode: str | None = None):
         super().__init__(path, tags, device, distributed_weights)
+        # a uint8 [H, W, 3] image feed takes JPEG byte strings as records: "host" / "device"
+        # (PipelinedGpuRunner jpeg_decode); None = EngineConfig's
+        self.jpeg_decode = jpeg_decode
         # staggered start of the compute lanes (batching/engine.py ``lane_offset_us``)
         self.lane_offset_us = float(lane_offset_us)
         # token-id signatures (BERT-style, mask computed from the ids): padding-free plans
@@ -122,8 +126,17 @@ class SignatureBatchedModel(SavedModel_, BatchedGpuModel):
             LOG.info("signature %s: ops run as PyTorch glue in the compiled plans: %s", self.signature, glue)
         self._runner = PipelinedGpuRunner(lanes, self._feed, lambda p: p.output_tensors(), self._shape,
                                           self._dtype.torch, depth=self.depth, device=dev,
-                                          lane_offset_us=getattr(self, "lane_offset_us", 0.0))
+                                          lane_offset_us=getattr(self, "lane_offset_us", 0.0),
+                                          jpeg_decode=self._jpeg_decode())
         self._version = getattr(sess.variables, "version", 0)
+
+    def _jpeg_decode(self) -> str:
+        """The runner's JPEG mode: the model's or the engine's choice for an image feed
+        (uint8 ``[H, W, 3]``), "host" for every other feed (which takes no JPEG records)."""
+        from ..config import current
+
+        image = len(self._shape) == 3 and self._shape[2] == 3 and self._dtype.torch == torch.uint8
+        return (getattr(self, "jpeg_decode", None) or current().jpeg_decode) if image else "host"
 
     def close(self) -> None:
         if self._runner is not None:
@@ -136,6 +149,8 @@ class SignatureBatchedModel(SavedModel_, BatchedGpuModel):
 
     # ------------------------------------------------------------------ batched GPU API
     def _as_array(self, r) -> np.ndarray:
+        if isinstance(r, (bytes, bytearray)) and self._runner is not None and self._runner._is_jpeg([r]):
+            return r  # a compressed image for an image feed: decoded by the runner into the staging slot
         if isinstance(r, TensorValue):
             r = r.to_numpy()
         elif isinstance(r, torch.Tensor):

@@ -32,8 +32,11 @@ class ImageClassifierModel(GenericModel, BatchedGpuModel):
                  buckets: Sequence[int] = (64, 256), top_k: int = 5, labels: Sequence[str] | None = None,
                  feed: str = "images:0", fetches: Sequence[str] = ("top_k:0", "top_k:1"), depth: int = 3,
                  device=None, use_graph: bool = True, precision: str = "bf16", calibration_images=None,
-                 distributed_weights: bool = False, lanes: int = 2, lane_offset_us: float = 0.0):
+                 distributed_weights: bool = False, lanes: int = 2, lane_offset_us: float = 0.0,
+                 jpeg_decode: str | None = None):
         super().__init__(device)
+        # JPEG records: "host" / "device" (PipelinedGpuRunner jpeg_decode); None = EngineConfig's
+        self.jpeg_decode = jpeg_decode
         self.lanes = max(1, int(lanes))  # concurrent plan instances on their own HIP streams
         # lane phase at a pipeline restart (PipelinedGpuRunner): off by default — under light
         # load every batch that overlaps a running one would wait; throughput runs set it
@@ -67,7 +70,7 @@ class ImageClassifierModel(GenericModel, BatchedGpuModel):
         if dev.type == "cuda":
             from ...batching.arena import DeviceArena
             from ...batching.engine import PipelinedGpuRunner
-            from ...config import EngineConfig
+            from ...config import EngineConfig, current
 
             H, W = self.image_hw
             # per compute lane one arena: its bucket plans share that arena's activation slab
@@ -87,7 +90,8 @@ class ImageClassifierModel(GenericModel, BatchedGpuModel):
             self._runner = PipelinedGpuRunner(lanes, self.feed, lambda p: p.output_tensors(), (H, W, 3),
                                               torch.uint8, depth=self.depth, device=dev,
                                               lane_offset_us=getattr(self, "lane_offset_us", 0.0),
-                                              decode_threads=getattr(self, "decode_threads", None))
+                                              decode_threads=getattr(self, "decode_threads", None),
+                                              jpeg_decode=getattr(self, "jpeg_decode", None) or current().jpeg_decode)
 
     def _calibration(self, b: int):
         if self.precision != "fp8" or self.calibration_images is None:

@@ -732,6 +732,36 @@ def preprocess_images(images_u8: torch.Tensor, out_hw=(224, 224), mean=(117.0, 1
     return out
 
 
+def jpeg_idct_rgb(coef: torch.Tensor, headers: torch.Tensor, out: torch.Tensor, n: int, H: int, W: int,
+                  stream: int | None = None, threads: int = 8) -> torch.Tensor:
+    """The arithmetic half of the JPEG decode: ``n`` coefficient rows (``coef[i]``, one
+    contiguous row of int16 coefficients per image, viewed as any dtype) and their headers
+    (``_native.jpeg_entropy_into``) -> RGB ``out[i]`` of uint8 ``[H, W, 3]``.  Images whose
+    header status is non-zero are skipped: their rows are not touched.  On the GPU the HIP
+    kernel (``kernels/jpeg.hip``) on ``stream`` (None: the current one), no allocation, no
+    synchronisation; on the host the scalar back half of ``csrc/jpeg.cpp`` on ``threads``
+    pool threads — the same arithmetic, so both give the same bytes."""
+    if out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (H, W, 3) or not out.is_contiguous():
+        raise ValueError(f"jpeg_idct_rgb: out must be contiguous uint8 [n, {H}, {W}, 3]")
+    if coef.dim() != 2 or headers.dim() != 2 or not coef.is_contiguous() or not headers.is_contiguous():
+        raise ValueError("jpeg_idct_rgb: coef and headers are contiguous [n, row bytes]")
+    if n < 0 or n > min(coef.shape[0], headers.shape[0], out.shape[0]):
+        raise ValueError("jpeg_idct_rgb: n exceeds the rows given")
+    if coef.device != out.device or headers.device != out.device:
+        raise ValueError("jpeg_idct_rgb: coef, headers and out must be on one device")
+    stride = coef.shape[1] * coef.element_size()
+    hbytes = headers.shape[1] * headers.element_size()
+    if hbytes != _ext.native().jpeg_coeff_layout(H, W)[1]:
+        raise ValueError("jpeg_idct_rgb: headers are not jpeg_coeff_layout's size")
+    if out.is_cuda:
+        _hip().jpeg_idct_rgb(coef.data_ptr(), headers.data_ptr(), out.data_ptr(), n, H, W, stride,
+                             _stream() if stream is None else stream)
+    else:
+        _ext.native().jpeg_coeffs_to_rgb(coef.data_ptr(), n * stride, headers.data_ptr(), n * hbytes, out.data_ptr(),
+                                         n * H * W * 3, n, stride, H * W * 3, H, W, threads)
+    return out
+
+
 def s2d_stem_weights(w_hwio: torch.Tensor, H: int, W: int, pads):
     """Rewrites a stride-2 KxK conv over RGB (pads top/left even) as a stride-1
     ceil(K/2)² conv over the 2x2 space-to-depth input (16 channels, 12 used).
