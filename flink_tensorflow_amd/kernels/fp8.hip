@@ -1142,32 +1142,6 @@ void conv2d_nhwc_fp8_multi(uintptr_t x, uintptr_t w, uintptr_t scale, uintptr_t 
   FTM_CHECK_LAUNCH();
 }
 
-// Y[M, N] = act(Xq[M, K] . Wq[N, K]^T * scale + bias)
-void gemm_fp8(uintptr_t x, uintptr_t w, uintptr_t scale, uintptr_t bias, uintptr_t y, int M, int N, int K, int ldx,
-              int ldy, int in_bf16, float in_q, int out_fp8, float out_q, int act, uintptr_t stream, int cfg) {
-  const int ealign = out_fp8 ? 16 : 8;
-  if (K % 16 || ldx % 16) throw std::invalid_argument("gemm_fp8: K and ldx must be multiples of 16");
-  if (N % ealign || ldy % ealign) throw std::invalid_argument("gemm_fp8: N/ldy not a multiple of the output chunk");
-  if (M <= 0 || N <= 0) throw std::invalid_argument("gemm_fp8: empty problem");
-  if (!scale || !bias) throw std::invalid_argument("gemm_fp8: scale and bias pointers are required");
-  check_align(x, 16, "x");
-  check_align(w, 16, "w");
-  check_align(y, 16, "y");
-  check_align(scale, 16, "scale");
-  check_align(bias, 16, "bias");
-  Fp8Params p{};
-  p.prio = fp8_prio();
-  p.x = reinterpret_cast<const uint8_t*>(x);
-  p.w = reinterpret_cast<const uint8_t*>(w);
-  p.scale = reinterpret_cast<const float*>(scale);
-  p.bias = reinterpret_cast<const float*>(bias);
-  p.y = reinterpret_cast<uint8_t*>(y);
-  p.in_q = in_q;
-  p.out_q = out_q;
-  p.M = M; p.Cout = N; p.K = K; p.ldx = ldx; p.ldy = ldy; p.y_coff = 0;
-  launch_io<false>(p, in_bf16, out_fp8, act, cfg, reinterpret_cast<hipStream_t>(stream));
-}
-
 void quantize_bf16_fp8(uintptr_t x, uintptr_t y, long n, float q, uintptr_t stream) {
   if (n % 16) throw std::invalid_argument("quantize_bf16_fp8: n % 16 != 0");
   check_align(x, 16, "x");
@@ -1192,6 +1166,9 @@ void dequantize_fp8_bf16(uintptr_t x, uintptr_t y, long n, float s, uintptr_t st
 void pool2d_nhwc_fp8(uintptr_t x, uintptr_t y, int N, int H, int W, int C, int Ho, int Wo, int kh, int kw, int sh,
                      int sw, int ph, int pw, int ldy, int y_coff, int is_max, float rq, uintptr_t stream) {
   if (C % 16 || ldy % 16 || y_coff % 16) throw std::invalid_argument("pool2d_nhwc_fp8: C/ldy/y_coff % 16 != 0");
+  if (N <= 0 || Ho <= 0 || Wo <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0)
+    throw std::invalid_argument("pool2d_nhwc_fp8: empty problem");
+  if (y_coff < 0 || y_coff + C > ldy) throw std::invalid_argument("pool2d_nhwc_fp8: channel slot exceeds the output row");
   check_align(x, 16, "x");
   check_align(y, 16, "y");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1287,7 +1264,6 @@ void global_avgpool_fp8(uintptr_t x, uintptr_t y, int N, int HW, int C, float s,
 
 void register_fp8(pybind11::module_& m) {
   m.def("conv2d_nhwc_fp8", &conv2d_nhwc_fp8);
-  m.def("gemm_fp8", &gemm_fp8);
   m.def("quantize_bf16_fp8", &quantize_bf16_fp8);
   m.def("dequantize_fp8_bf16", &dequantize_fp8_bf16);
   m.def("pool2d_nhwc_fp8", &pool2d_nhwc_fp8);

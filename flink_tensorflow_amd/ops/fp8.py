@@ -203,6 +203,9 @@ def pool2d_nhwc_fp8(x: torch.Tensor, ksize, stride, pad=(0, 0, 0, 0), mode="max"
     if out is None:
         out = torch.empty((N, Ho, Wo, C), dtype=torch.uint8, device=x.device)
         out_channel_offset = 0
+    if tuple(out.shape[:3]) != (N, Ho, Wo) or out_channel_offset < 0 or out_channel_offset + C > out.shape[3]:
+        raise ValueError(f"pool2d_nhwc_fp8: out {tuple(out.shape)} cannot hold [{N},{Ho},{Wo},{C}] at "
+                         f"offset {out_channel_offset}")
     if x.is_cuda:
         _check(x, "x", torch.uint8, x.device)
         _check(out, "out", torch.uint8, x.device)
