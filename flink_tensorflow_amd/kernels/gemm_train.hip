@@ -156,6 +156,7 @@ struct Operand {
 
 template <bool XT, bool WT, int ACT, bool F32, bool HAS_RES, bool SPLIT, int STAGES>
 __global__ __launch_bounds__(NT, STAGES == 2 ? 2 : 1) void gemm_train_kernel(TrParams p) {
+  static_assert(!HAS_RES || ACT == ACT_DRELU, "res is the ReLU-backward mask operand only");
   __shared__ __attribute__((aligned(1024))) uint8_t smem[lds_bytes<STAGES>()];
   const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
   const int tm = tile / p.tiles_n;
@@ -281,10 +282,7 @@ __global__ __launch_bounds__(NT, STAGES == 2 ? 2 : 1) void gemm_train_kernel(TrP
         bf16x8 o = __builtin_bit_cast(bf16x8, v);
         const bf16x8 r = *reinterpret_cast<const bf16x8*>(p.res + (size_t)m * p.ldr + n);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          if constexpr (ACT == ACT_DRELU) o[e] = (float)r[e] > 0.f ? o[e] : f2bf(0.f);
-          else o[e] = f2bf(apply_act<ACT>((float)o[e] + (float)r[e]));
-        }
+        for (int e = 0; e < 8; ++e) o[e] = (float)r[e] > 0.f ? o[e] : f2bf(0.f);
         v = __builtin_bit_cast(u32x4, o);
       }
       if (p.colsum) {
@@ -342,7 +340,7 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restr
 }
 
 // Split-K reduction: sum the fp32 slabs in slab order (deterministic), + bias, then fp32
-// out, or bf16 out with act / residual / ReLU-backward mask.  4 columns per thread.
+// out, or bf16 out with act / ReLU-backward mask.  4 columns per thread.
 template <int ACT, bool F32, bool HAS_RES>
 __global__ __launch_bounds__(256) void gemm_train_reduce_kernel(const float* __restrict__ part, int splits,
                                                                 long split_stride, const float* __restrict__ bias,
@@ -365,9 +363,7 @@ __global__ __launch_bounds__(256) void gemm_train_reduce_kernel(const float* __r
     for (int e = 0; e < 4; ++e) {
       float v = a[e];
       if constexpr (HAS_RES) {
-        const float r = (float)res[(size_t)m * ldr + n + e];
-        if constexpr (ACT == ACT_DRELU) v = r > 0.f ? v : 0.f;
-        else v = apply_act<ACT>(v + r);
+        v = (float)res[(size_t)m * ldr + n + e] > 0.f ? v : 0.f;
       } else {
         v = apply_act<ACT>(v);
       }
@@ -414,14 +410,13 @@ void dispatch_epi(const TrParams& p, int act, bool f32, int splits, float* ws, h
     launch_tr<XT, WT, ACT_NONE, true, false>(p, splits, ws, s);
     return;
   }
+  if (p.res && act != ACT_DRELU) throw std::invalid_argument("gemm_train: res is the drelu mask operand (act must be drelu)");
   switch (act) {
     case ACT_NONE:
-      if (p.res) launch_tr<XT, WT, ACT_NONE, false, true>(p, splits, ws, s);
-      else launch_tr<XT, WT, ACT_NONE, false, false>(p, splits, ws, s);
+      launch_tr<XT, WT, ACT_NONE, false, false>(p, splits, ws, s);
       break;
     case ACT_RELU:
-      if (p.res) launch_tr<XT, WT, ACT_RELU, false, true>(p, splits, ws, s);
-      else launch_tr<XT, WT, ACT_RELU, false, false>(p, splits, ws, s);
+      launch_tr<XT, WT, ACT_RELU, false, false>(p, splits, ws, s);
       break;
     case ACT_DRELU:
       if (!p.res) throw std::invalid_argument("gemm_train: the drelu epilogue needs the mask operand (res)");

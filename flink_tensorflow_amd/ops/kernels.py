@@ -423,14 +423,16 @@ def gemm_train(x: torch.Tensor, w: torch.Tensor, *, x_t: bool = False, w_t: bool
     ``w`` [N, K] or, with ``w_t``, ``w`` stored [K, N] — so a dense layer's three GEMMs need
     no transposed copies: forward ``gemm_train(h, W)``, dX ``gemm_train(dA, W, w_t=True)``,
     dW ``gemm_train(dA, h, x_t=True, w_t=True, out_dtype=torch.float32)``.  ``mask`` (bf16
-    [M, N], e.g. the layer input) applies the ReLU backward ``mask > 0 ? y : 0``; ``out`` may
-    be a row-strided view.  fp32 output takes no activation.  ``splits`` > 1 runs split-K
+    [M, N], e.g. the layer input) applies the ReLU backward ``mask > 0 ? y : 0`` (and takes no
+    other activation); ``out`` and ``mask`` may be row-strided views.  fp32 output takes no activation.  ``splits`` > 1 runs split-K
     (None: cost model) with an fp32 workspace ``ws`` (>= splits*M*N floats).  ``colsum``
     (fp32 [ceil(M/128), N], bf16 output, no split) receives every 128-row tile's column sums
     of the stored values — ``colsum_reduce`` turns them into the next layer's bias gradient.
     K must be a multiple of 8 (a partial last K tile reads zeros)."""
     a = act_code(act)
     if mask is not None:
+        if a not in (ACT_NONE, ACT_DRELU):
+            raise ValueError("gemm_train: mask is the ReLU-backward operand; it takes no other activation")
         a = ACT_DRELU
     M, K = (x.shape[1], x.shape[0]) if x_t else (x.shape[0], x.shape[1])
     N, K2 = (w.shape[1], w.shape[0]) if w_t else (w.shape[0], w.shape[1])
@@ -465,8 +467,9 @@ def gemm_train(x: torch.Tensor, w: torch.Tensor, *, x_t: bool = False, w_t: bool
     if bias is not None:
         _check(bias, "bias", torch.float32, x.device)
     if mask is not None:
-        _check(mask, "mask", device=x.device)
-        if tuple(mask.shape) != (M, N) or mask.stride(1) != 1:
+        if mask.dtype != torch.bfloat16 or mask.device != x.device:
+            raise ValueError(f"gemm_train: mask must be bf16 on {x.device}")
+        if tuple(mask.shape) != (M, N) or mask.stride(1) != 1:  # a row-strided view is fine (ldr = stride(0))
             raise ValueError("gemm_train: mask must be [M, N] with contiguous rows")
     if colsum is not None:
         if f32 or tuple(colsum.shape) != (-(-M // 128), N) or colsum.dtype != torch.float32 or not colsum.is_contiguous():
