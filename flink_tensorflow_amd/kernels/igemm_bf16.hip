@@ -421,6 +421,8 @@ void conv2d_nhwc_bf16(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t res, u
   if (N <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) throw std::invalid_argument("conv2d_nhwc_bf16: empty problem");
   if ((long)N * H * W * Cin * 2 >= (1L << 31) || (long)N * Ho * Wo >= (1L << 31))
     throw std::invalid_argument("conv2d_nhwc_bf16: tensor too large for 32-bit (byte) indexing");
+  if ((long)Cout * KH * KW * Cin * 2 >= (1L << 31))
+    throw std::invalid_argument("conv2d_nhwc_bf16: weights too large for 32-bit (byte) indexing");
   if (KH * KW > 64) throw std::invalid_argument("conv2d_nhwc_bf16: more than 64 filter taps");
   check_align(x, 16, "x");
   check_align(w, 16, "w");
@@ -456,6 +458,9 @@ void gemm_bf16(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t res, uintptr_
   if (N % 8 || ldy % 8) throw std::invalid_argument("gemm_bf16: N and ldy must be multiples of 8");
   if (res && ldr % 8) throw std::invalid_argument("gemm_bf16: residual stride % 8 != 0");
   if (M <= 0 || N <= 0) throw std::invalid_argument("gemm_bf16: empty problem");
+  // the kernel keeps X row offsets (elements) and W row offsets (bytes) in 32 bits
+  if ((long)M * ldx >= (1L << 31) || (long)N * K * 2 >= (1L << 31))
+    throw std::invalid_argument("gemm_bf16: tensor too large for 32-bit indexing");
   check_align(x, 16, "x");
   check_align(w, 16, "w");
   check_align(y, 16, "y");
@@ -483,7 +488,8 @@ void conv1x1_dual_bf16(uintptr_t x, uintptr_t x2, uintptr_t w, uintptr_t bias, u
   if (K1 % 8 || C2 % 8 || Cout % 8 || ldy % 8 || y_coff % 8)
     throw std::invalid_argument("conv1x1_dual_bf16: channel counts must be multiples of 8");
   if ((Ho - 1) * s2 >= H2 || (Wo - 1) * s2 >= W2) throw std::invalid_argument("conv1x1_dual_bf16: shortcut geometry");
-  if ((long)N * H2 * W2 * C2 >= (1L << 31) || (long)N * Ho * Wo * K1 >= (1L << 31))
+  if ((long)N * H2 * W2 * C2 >= (1L << 31) || (long)N * Ho * Wo * K1 >= (1L << 31) ||
+      (long)Cout * (K1 + C2) * 2 >= (1L << 31))
     throw std::invalid_argument("conv1x1_dual_bf16: tensor too large for 32-bit indexing");
   require_bias(reinterpret_cast<const float*>(bias));
   check_align(x, 16, "x");

@@ -1167,6 +1167,12 @@ def conv1x1_dual(x: torch.Tensor, x2: torch.Tensor, w_cat: torch.Tensor, bias: t
     if out is None:
         out = torch.empty((N, Ho, Wo, Cout), dtype=x.dtype if x.is_cuda else torch.float32, device=x.device)
         out_channel_offset = 0
+    if x2.shape[0] != N or (Ho - 1) * stride2 >= H2 or (Wo - 1) * stride2 >= W2:
+        raise ValueError(f"conv1x1_dual: shortcut source {tuple(x2.shape)} at stride {stride2} does not cover "
+                         f"[{N},{Ho},{Wo}]")
+    if out.shape[:3] != (N, Ho, Wo) or out_channel_offset + Cout > out.shape[3]:
+        raise ValueError(f"conv1x1_dual: out {tuple(out.shape)} cannot hold [{N},{Ho},{Wo},{Cout}] at "
+                         f"offset {out_channel_offset}")
     a = act_code(act)
     if x.is_cuda:
         for t, n in ((x, "x"), (x2, "x2"), (w_cat, "w"), (out, "out")):
