@@ -960,8 +960,9 @@ class ConvLowering:
         stem output, kept alive until it) instead of reading the 256-channel tensor, and the
         previous tail stops storing it.  Chains start at the dual (projection) tail and hold
         up to ``chain_max_links`` links (2: tail 1 -> tail 2, the third tail reads y3 again;
-        three links recompute more than the saved traffic buys: 77.6-77.8k vs 79.3-79.6k,
-        profiles/r06_chain)."""
+        three links still recompute more than the saved traffic buys, also on the
+        rescheduled kernels: stage-1 tails 100 + 154 + 256 us against 102 + 176 + 161,
+        79.1-80.1k vs 80.6-81.5k records/s, profiles/r07_tail_sched)."""
         if not _cfg().recompute_tails:
             return
         fetched = self._fetched_roots()

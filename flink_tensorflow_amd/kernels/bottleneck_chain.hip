@@ -30,6 +30,14 @@
 //     pass     (STORE) coalesced 16-B chunks of Y -> y3 in HBM, decimated or not
 //     phase 2  y1 = relu(Y . W1^T + b1): wave w owns one 16-channel fragment of W1 (32 VGPRs)
 //              and 64 / (CN / 16 / 8 * 16) pixel fragments; staged in O, coalesced stores
+//   Schedule.  Phase 1 is a pipeline of 64-deep steps (half, source tile): the B fragments
+//   of step s + 1 are read into a second register set before the MFMAs of step s issue, and
+//   a link's finish (bias, roundings, residual, relu: VALU) is issued beside the MFMAs of
+//   the next step, which accumulate into the other accumulator set and depend only on the
+//   sources.  Phase 2 reads the Y fragments of K-step ks + 1 before the MFMAs of ks
+//   (sched_barrier pins the order); the y3 pass issues all its Y reads before its first
+//   store.  The link biases live in registers: a global load inside the tile would queue
+//   behind the next tile's LDS-DMA in vmcnt order and wait for it.
 //     (a first version staged the sources through registers during phase 2: every tile
 //     then waited one HBM latency, 130 / 183 / 303 µs for J = 1 / 2 / 3 at micro-batch 256
 //     against 175 / 199 / 197 µs for the unfused tails: profiles/r06_f)
@@ -115,6 +123,14 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks)
     wb[ks] = *reinterpret_cast<const bf16x8*>(p.w1 + (size_t)(cf * 16 + prow) * CO + ks * 32 + kg * 8);
+  // biases of this wave's channels, resident too (a load inside the tile would queue behind
+  // the next tile's LDS-DMA in vmcnt order)
+  f32x4 bl[J][2];
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) bl[j][i] = *reinterpret_cast<const f32x4*>(p.l[j].b + wave * 32 + i * 16 + kg * 4);
+  const f32x4 bv1 = *reinterpret_cast<const f32x4*>(p.b1 + cf * 16 + kg * 4);
 
   // ---- source staging by LDS-DMA: piece k (1 KiB = 8 pixel rows x 8 chunks) of source
   // k / 8; lane l writes LDS slot l of the piece: row 8 (k % 8) + l / 8, slot l % 8, which
@@ -142,32 +158,36 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
     }
   };
 
-  // one 64-deep link of phase 1 from source tile X, pixel fragments j0 .. j0 + PF / 2 - 1
-  auto mma64 = [&](f32x4 (&acc)[2][PF / 2], const bf16x8 (&wa)[2][2], const u32x4* X, int j0) {
+  constexpr int PH = PF / 2;  // phase 1 runs in two halves of PH pixel fragments
+  // the B fragments of one 64-deep step: source tile src of stage X, pixel fragments j0 ..
+  auto read_src = [&](bf16x8 (&dst)[2][PH], const u32x4* X, int src, int j0) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = ks * 4 + kg;
+    for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int j = 0; j < PF / 2; ++j) {
-        const bf16x8 b = __builtin_bit_cast(bf16x8, X[swz<8>((j0 + j) * 16 + prow, c)]);
+      for (int j = 0; j < PH; ++j)
+        dst[ks][j] = __builtin_bit_cast(bf16x8, X[src * TP * 8 + swz<8>((j0 + j) * 16 + prow, ks * 4 + kg)]);
+  };
+  // one 64-deep step of phase 1 on fragments already in registers
+  auto mma64 = [&](f32x4 (&acc)[2][PH], const bf16x8 (&w0)[2], const bf16x8 (&w1)[2], const bf16x8 (&xb)[2][PH]) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[i][ks], b, acc[i][j], 0, 0, 0);
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int j = 0; j < PH; ++j) {
+        acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[ks], xb[ks][j], acc[0][j], 0, 0, 0);
+        acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[ks], xb[ks][j], acc[1][j], 0, 0, 0);
       }
-    }
   };
   // acc + b -> bf16, + residual (the previous link's y3, bf16-exact floats), relu -> bf16
-  auto finish = [&](f32x4 (&acc)[2][PF / 2], f32x4 (&res)[2][PF / 2], const float* b, bool first) {
+  auto finish = [&](const f32x4 (&acc)[2][PH], f32x4 (&res)[2][PH], const f32x4 (&bv)[2], bool first) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(b + wave * 32 + i * 16 + kg * 4);
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < PF / 2; ++j)
+      for (int j = 0; j < PH; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float v = (float)f2bf(acc[i][j][r] + bv[r]);
+          const float v = (float)f2bf(acc[i][j][r] + bv[i][r]);
           res[i][j][r] = (float)f2bf(fmaxf(first ? v : v + res[i][j][r], 0.f));
         }
-    }
   };
   // y1 of the previous tile out of O (coalesced 16-B chunks)
   auto store_y1 = [&](int pt) {
@@ -179,6 +199,7 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
     }
   };
 
+  const int nwg = gridDim.x;  // read once: the asm memory clobber below would reload it per tile
   int t = blockIdx.x;
   int stage = 0;
   int prev = -1;  // tile whose y1 waits in O
@@ -193,54 +214,63 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
     if (prev >= 0) store_y1(prev);  // O is read before phase 2 rewrites it (a barrier between)
-    const int tn = t + gridDim.x;
+    const int tn = t + nwg;
     const bool more = tn < ntiles;
     if (more) dma(tn, stage ^ 1);  // the next tile's sources, in flight during this whole tile
     const u32x4* X = reinterpret_cast<const u32x4*>(smem + stage * XB);
     // ---- phase 1: the chain, y3 of channels 32w .. 32w + 31 in registers, in two halves
-    // of 32 pixels (the chain is per pixel: half the accumulators live at a time)
+    // of 32 pixels (the chain is per pixel: half the accumulators live at a time), as a
+    // pipeline of 64-deep steps st = (half, source tile): the fragments of step st + 1 are
+    // read into the other half of xb before the MFMAs of st issue, and a link's finish
+    // (VALU) is issued with the MFMAs of the step after its last, which go to the other
+    // accumulator set and depend on the sources only
+    {
+      constexpr int NST = 2 * S;
+      f32x4 y[2][PH], acc[2][2][PH];
+      bf16x8 xb[2][2][PH];
+      // finish link `link` of `half` out of accumulator set a; the last link's y3 goes into Y:
+      // y[i][j][r] = channel 32w + 16i + 4kg + r of pixel 16 (half PH + j) + prow
+      auto complete = [&](int half, int link, int a) {
+        finish(acc[a], y, bl[link], link == 0);
+        if (link == J - 1) {
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      constexpr int PH = PF / 2;
-      f32x4 y[2][PH], acc[2][PH];
-      auto zero = [&]() {
+          for (int i = 0; i < 2; ++i) {
+            const int co = wave * 32 + i * 16 + kg * 4;
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < PH; ++j) {
+              bf16x4 o;
 #pragma unroll
-          for (int j = 0; j < PH; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+              for (int r = 0; r < 4; ++r) o[r] = f2bf(y[i][j][r]);
+              bf16* chunk = reinterpret_cast<bf16*>(Ys + swz<32>((half * PH + j) * 16 + prow, co >> 3));
+              *reinterpret_cast<bf16x4*>(chunk + (co & 7)) = o;
+            }
+          }
+        }
       };
-      const int j0 = half * PH;
-      zero();
-      {
-        const bf16x8 w0a[2][2] = {{wa0[0][0], wa0[0][1]}, {wa0[1][0], wa0[1][1]}};
-        const bf16x8 w0b[2][2] = {{wa0[0][2], wa0[0][3]}, {wa0[1][2], wa0[1][3]}};
-        mma64(acc, w0a, X, j0);  // [c1 | x0]: K 0..63 from c1, 64..127 from x0
-        mma64(acc, w0b, X + TP * 8, j0);
-      }
-      finish(acc, y, p.l[0].b, true);
-      if constexpr (J >= 2) {
-        zero();
-        mma64(acc, wa1, X + 2 * TP * 8, j0);
-        finish(acc, y, p.l[1].b, false);
-      }
-      if constexpr (J >= 3) {
-        zero();
-        mma64(acc, wa2, X + 3 * TP * 8, j0);
-        finish(acc, y, p.l[2].b, false);
-      }
-      // y3 into Y: y[i][j][r] = channel 32w + 16i + 4kg + r of pixel 16 (j0 + j) + prow
+      read_src(xb[0], X, 0, 0);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int co = wave * 32 + i * 16 + kg * 4;
+      for (int st = 0; st < NST; ++st) {
+        const int half = st / S, src = st % S;
+        const int link = src < 2 ? 0 : src - 1;  // sources 0, 1 = [c1 | x0] feed link 0
+        const int a = (half * J + link) & 1;     // accumulator sets alternate from link to link
+        if (st + 1 < NST) read_src(xb[(st + 1) & 1], X, (st + 1) % S, ((st + 1) / S) * PH);
+        if (src != 1) {
 #pragma unroll
-        for (int j = 0; j < PH; ++j) {
-          bf16x4 o;
+          for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = f2bf(y[i][j][r]);
-          bf16* chunk = reinterpret_cast<bf16*>(Ys + swz<32>((j0 + j) * 16 + prow, co >> 3));
-          *reinterpret_cast<bf16x4*>(chunk + (co & 7)) = o;
+            for (int j = 0; j < PH; ++j) acc[a][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if (src == 0) mma64(acc[a], {wa0[0][0], wa0[0][1]}, {wa0[1][0], wa0[1][1]}, xb[st & 1]);
+        else if (src == 1) mma64(acc[a], {wa0[0][2], wa0[0][3]}, {wa0[1][2], wa0[1][3]}, xb[st & 1]);
+        else if (src == 2) mma64(acc[a], wa1[0], wa1[1], xb[st & 1]);
+        else mma64(acc[a], wa2[0], wa2[1], xb[st & 1]);
+        // the link that ended with step st - 1 (every step but a half's first source ends one)
+        if (st > 0 && (st - 1) % S != 0) {
+          const int ph = (st - 1) / S, pl = (st - 1) % S - 1;
+          complete(ph, pl, (ph * J + pl) & 1);
         }
       }
+      complete(1, J - 1, (J + J - 1) & 1);
     }
     __syncthreads();  // Y complete; this stage's sources read
     if constexpr (STORE) {  // y3 to HBM in coalesced 16-B chunks (decimated: even (h, w) only)
@@ -252,8 +282,16 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
         dh = tt % p.dec_h;
         dn = tt / p.dec_h;
       }
+      constexpr int YIT = TP * CO / 8 / NT;
+      u32x4 yv[YIT];  // every Y read of the pass is issued before the first store
 #pragma unroll
-      for (int it = 0; it < TP * CO / 8 / NT; ++it) {
+      for (int it = 0; it < YIT; ++it) {
+        const int q = tid + it * NT;
+        yv[it] = Ys[swz<32>(q >> 5, q & 31)];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int it = 0; it < YIT; ++it) {
         const int q = tid + it * NT;
         const int pl = q >> 5, c = q & 31;
         int o = p0 + pl;
@@ -269,30 +307,36 @@ __global__ __launch_bounds__(NT, 1) void bottleneck_chain_kernel(ChainParams p) 
           st = st && !((dh | dw) & 1);
           o = (dn * (p.dec_h >> 1) + (dh >> 1)) * (p.dec_w >> 1) + (dw >> 1);
         }
-        if (st) reinterpret_cast<u32x4*>(p.y3 + (size_t)o * CO)[c] = Ys[swz<32>(pl, c)];
+        if (st) reinterpret_cast<u32x4*>(p.y3 + (size_t)o * CO)[c] = yv[it];
       }
     }
     // ---- phase 2: y1 = relu(Y . W1^T + b1): channel fragment cf, pixel fragments pf0 ..
     f32x4 acc2[PPW];
 #pragma unroll
     for (int q = 0; q < PPW; ++q) acc2[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    {  // the Y fragments of K-step ks + 1 are read into the other half of yb before the MFMAs of ks
+      bf16x8 yb[2][PPW];
+      auto read_y = [&](int ks, bf16x8 (&dst)[PPW]) {
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const int c = ks * 4 + kg;
+        for (int q = 0; q < PPW; ++q) dst[q] = __builtin_bit_cast(bf16x8, Ys[swz<32>((pf0 + q) * 16 + prow, ks * 4 + kg)]);
+      };
+      read_y(0, yb[0]);
 #pragma unroll
-      for (int q = 0; q < PPW; ++q) {
-        const bf16x8 b = __builtin_bit_cast(bf16x8, Ys[swz<32>((pf0 + q) * 16 + prow, c)]);
-        acc2[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[ks], b, acc2[q], 0, 0, 0);
+      for (int ks = 0; ks < 8; ++ks) {
+        if (ks + 1 < 8) read_y(ks + 1, yb[(ks + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);  // pins the order: reads of ks + 1, then MFMAs of ks
+#pragma unroll
+        for (int q = 0; q < PPW; ++q) acc2[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[ks], yb[ks & 1][q], acc2[q], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
     {
       const int co = cf * 16 + kg * 4;
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(p.b1 + co);
 #pragma unroll
       for (int q = 0; q < PPW; ++q) {
         bf16x4 o;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = f2bf(fmaxf(acc2[q][r] + bv[r], 0.f));
+        for (int r = 0; r < 4; ++r) o[r] = f2bf(fmaxf(acc2[q][r] + bv1[r], 0.f));
         bf16* chunk = reinterpret_cast<bf16*>(Os + swz<CN / 8>((pf0 + q) * 16 + prow, co >> 3));
         *reinterpret_cast<bf16x4*>(chunk + (co & 7)) = o;
       }
