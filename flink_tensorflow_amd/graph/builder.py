@@ -114,6 +114,14 @@ class GraphBuilder:
     def relu(self, x, name=None) -> str:
         return self.op("Relu", [x], name=name)
 
+    def relu6(self, x, name=None) -> str:
+        return self.op("Relu6", [x], name=name)
+
+    def depthwise_conv2d(self, x, w, strides=(1, 1), padding="SAME", name=None, dilations=(1, 1)) -> str:
+        """``w`` is ``[KH, KW, C, channel_multiplier]``."""
+        return self.op("DepthwiseConv2dNative", [x, w], name=name, strides=[1, strides[0], strides[1], 1],
+                       padding=padding.encode(), data_format=b"NHWC", dilations=[1, dilations[0], dilations[1], 1])
+
     def conv2d(self, x, w, strides=(1, 1), padding="SAME", name=None, dilations=(1, 1)) -> str:
         return self.op("Conv2D", [x, w], name=name, strides=[1, strides[0], strides[1], 1], padding=padding.encode(),
                        data_format=b"NHWC", dilations=[1, dilations[0], dilations[1], 1], use_cudnn_on_gpu=True)

@@ -12,6 +12,9 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``Conv2D → [BiasAdd | FusedBatchNorm]* → [Add(residual)] → [Relu|Relu6]`` → one
      implicit-GEMM conv launch with BN folded into the weights and a bias+residual+act
      epilogue;
+   * ``DepthwiseConv2dNative → [BiasAdd | FusedBatchNorm]* → [Relu|Relu6]`` → one launch of
+     the depthwise kernel (3x3 register-tiled or generic), BN folded into the per-channel
+     filter; a residual ``Add`` behind it stays an elementwise step;
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -402,6 +405,8 @@ class CompiledFunction(TransformerLowering, ConvLowering):
         op = node.op
         if op == "Conv2D":
             return self._lower_conv(node)
+        if op == "DepthwiseConv2dNative":
+            return self._lower_dwconv(node)
         if op == "MatMul":
             return self._lower_matmul(node)
         if op == "Cast" and self._try_preprocess(node):

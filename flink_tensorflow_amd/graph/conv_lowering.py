@@ -6,7 +6,8 @@ The kernel choice of a single conv is a pure function of a :class:`ConvSite`
 The fusions that depend on plan state — the preprocess fold and the fused max pool of the
 direct conv, the projection shortcut, the bottleneck block tail, the sibling group of an
 Inception module, the commuted average pool — stay methods, as do the two post-passes that
-rewrite block tails (``_decimate_tails``, ``_chain_tails``)."""
+rewrite block tails (``_decimate_tails``, ``_chain_tails``).  A ``DepthwiseConv2dNative``
+chain has one kernel (kernels/dwconv.hip) and one lowering, ``_lower_dwconv``."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -34,6 +35,8 @@ LITE_FP8_CFG = 11
 _PP_MIN_K = 512
 
 _PLAIN_ACTS = (K.ACT_NONE, K.ACT_RELU)
+# the depthwise kernel's epilogue: Sigmoid / Tanh end its chain before them
+_DW_ACTS = {"Relu": K.ACT_RELU, "Relu6": K.ACT_RELU6}
 
 
 @dataclass(frozen=True)
@@ -154,8 +157,10 @@ class _ConvJob:
 
 class ConvLowering:
     # ---- conv chain
-    def _conv_chain(self, start: Node):
-        """Follows Conv2D/MatMul → BiasAdd/FusedBatchNorm* → Add(res)? → act? ."""
+    def _conv_chain(self, start: Node, absorb_residual: bool = True, acts=_ACTS):
+        """Follows Conv2D/MatMul → BiasAdd/FusedBatchNorm* → Add(res)? → act? .  Without
+        ``absorb_residual`` a residual Add ends the chain before it (the depthwise kernel has
+        no residual operand); ``acts`` are the activations the kernel's epilogue has."""
         scale = None
         bias = None
         residual = None
@@ -174,7 +179,7 @@ class ConvLowering:
                 if ov is not None and ov.is_const and ov.const.dim() == 1:
                     b = ov.const.float()
                     bias = b if bias is None else bias + b
-                elif nxt.op != "BiasAdd" and ov is not None and not ov.is_const:
+                elif nxt.op != "BiasAdd" and ov is not None and not ov.is_const and absorb_residual:
                     residual = (nxt, other[0])
                 else:
                     break
@@ -190,8 +195,8 @@ class ConvLowering:
                 shift = b - m * s
                 scale = s if scale is None else scale * s
                 bias = shift if bias is None else bias * s + shift
-            elif nxt.op in _ACTS and act == K.ACT_NONE:
-                act = _ACTS[nxt.op]
+            elif nxt.op in acts and act == K.ACT_NONE:
+                act = acts[nxt.op]
             else:
                 break
             absorbed.append(nxt)
@@ -257,6 +262,53 @@ class ConvLowering:
         # 5. one launch step
         {"dconv": self._emit_dconv, "conv3x3c64": self._emit_conv3x3c64, "gemm_pp": self._emit_gemm_pp,
          "pw_res": self._emit_pw_res, "conv_lite": self._emit_conv_lite, "igemm": self._emit_igemm}[impl](c)
+
+    # ---- depthwise conv
+    def _lower_dwconv(self, node: Node):
+        """``DepthwiseConv2dNative → [BiasAdd | FusedBatchNorm*]* → [Relu | Relu6]`` as one
+        launch of the depthwise kernel (kernels/dwconv.hip); the BN scale of channel ``c``
+        multiplies ``w[:, :, c, 0]``.  A residual Add stays an elementwise step."""
+        x = self._in(node, 0)
+        wv = self._in(node, 1)
+        if (not wv.is_const or node.attr("data_format", "NHWC") != "NHWC" or len(x.shape) != 4
+                or len(wv.const.shape) != 4 or wv.const.shape[3] != 1 or x.is_const
+                or node.attr("padding", "SAME") not in ("SAME", "VALID")):
+            return self._lower_glue(node)
+        w = wv.const.float()  # [KH, KW, C, 1]
+        KH, KW, C, _ = w.shape
+        N, H, W, Cx = x.shape
+        strides = node.attr("strides")
+        dil = node.attr("dilations") or [1, 1, 1, 1]
+        stride, dil = (strides[1], strides[2]), (dil[1], dil[2])
+        if Cx != C or x.phys_c or not K.dwconv_eligible(C, KH, KW, stride, dil) \
+                or not (x.dtype in (torch.bfloat16, torch.float32) or x.qscale is not None):
+            return self._lower_glue(node)
+        if node.attr("padding", "SAME") == "SAME":
+            pads = (*same_pads(H, KH, stride[0], dil[0]), *same_pads(W, KW, stride[1], dil[1]))
+        else:
+            pads = (0, 0, 0, 0)
+        Ho = (H + pads[0] + pads[1] - ((KH - 1) * dil[0] + 1)) // stride[0] + 1
+        Wo = (W + pads[2] + pads[3] - ((KW - 1) * dil[1] + 1)) // stride[1] + 1
+        if Ho < 1 or Wo < 1:
+            return self._lower_glue(node)
+        last, scale, bias, _, act, absorbed = self._conv_chain(node, absorb_residual=False, acts=_DW_ACTS)
+        w = w[..., 0]
+        if scale is not None:
+            w = w * scale
+        w_dev = self._dev(w.reshape(KH * KW, C).contiguous(), torch.bfloat16)
+        b_dev = self._dev(bias, torch.float32) if bias is not None else None
+        self.params += [w_dev] + ([b_dev] if b_dev is not None else [])
+        xin = self._as_bf16(x, node.name)
+        out = self._new((N, Ho, Wo, C))
+        for a in absorbed:
+            self._fused.add(a.name)
+
+        def run(xin=xin, out=out, w_dev=w_dev, b_dev=b_dev):
+            K.dwconv2d_nhwc(xin.buf, w_dev, b_dev, stride, pads, dil, act, out=_target(out),
+                            out_channel_offset=_coff(out), kernel=(KH, KW))
+
+        self._emit(node.name, "dwconv", run, [xin], [out], {"impl": K.dwconv_impl(KH, KW, stride, dil)})
+        self._finish_conv(last, absorbed, out)
 
     def _prepare_conv(self, node, x, w, bias, residual, act, last, absorbed, stride, pads, dil, out_hw) -> _ConvJob:
         """Weights, input and output values of a bf16 conv chain, and its ``ConvSite``."""

@@ -211,6 +211,25 @@ class ResNet50Model(ImageClassifierModel):
         return resnet50_graph_def(image_hw=self.image_hw, top_k=self.top_k, seed=self.seed, depth=self.depth_layers)
 
 
+class MobileNetV1Model(ImageClassifierModel):
+    """MobileNet-V1 (random-init frozen graph): the depthwise layers run on the depthwise
+    kernel, the stem and pointwise layers on the implicit GEMM, so the plan is strict."""
+
+    def __init__(self, image_hw=(256, 256), buckets=(64, 256), top_k=5, seed: int = 0, device=None,
+                 alpha: float = 1.0, out_hw=(224, 224), num_classes: int = 1000, **kw):
+        self.seed = seed
+        self.alpha = alpha
+        self.out_hw = tuple(out_hw)
+        self.num_classes = num_classes
+        super().__init__(self._make_graph, image_hw, buckets, top_k, device=device, **kw)
+
+    def _make_graph(self) -> GraphDef:
+        from .mobilenet import mobilenet_v1_graph_def
+
+        return mobilenet_v1_graph_def(alpha=self.alpha, num_classes=self.num_classes, seed=self.seed,
+                                      image_hw=self.image_hw, out_hw=self.out_hw, top_k=self.top_k)
+
+
 class InceptionV3Model(ImageClassifierModel):
     """Inception-v3 (random-init frozen graph) compiled for fp8 by default — BASELINE config
     5: e4m3 weights and activations on the CDNA4 fp8 MFMA, bucketed dynamic batching per

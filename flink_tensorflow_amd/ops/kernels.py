@@ -794,6 +794,85 @@ def s2d_stem_weights(w_hwio: torch.Tensor, H: int, W: int, pads):
     return w2, (pt_b, pb_b, pl_b, pr_b)
 
 
+# ------------------------------------------------------------------------------ depthwise conv
+# output tile per thread of the 3x3 kernel (kernels/dwconv.hip); 0 = the launcher's choice
+DWCONV_TILES = {"1x4": 1, "2x2": 2}
+DWCONV_GENERIC = -1
+
+
+def dwconv_eligible(C: int, KH: int, KW: int, stride=(1, 1), dilation=(1, 1)) -> bool:
+    """What ``dwconv_nhwc_bf16`` takes: 8-channel vectors, a filter of at most 7x7."""
+    return (C > 0 and C % 8 == 0 and 1 <= KH <= 7 and 1 <= KW <= 7 and min(stride) >= 1 and min(dilation) >= 1)
+
+
+def dwconv_impl(KH: int, KW: int, stride=(1, 1), dilation=(1, 1)) -> str:
+    """The kernel the host launcher picks: the register-tiled 3x3 (dilation 1, stride 1 or
+    2: every MobileNet layer) or the generic one."""
+    if (KH, KW) == (3, 3) and tuple(dilation) == (1, 1) and tuple(stride) in ((1, 1), (2, 2)):
+        return "dwconv3x3"
+    return "dwconv_generic"
+
+
+def dwconv2d_nhwc(x: torch.Tensor, w_taps_c: torch.Tensor, bias: torch.Tensor | None = None, stride=(1, 1),
+                  pad=(0, 0, 0, 0), dilation=(1, 1), act=None, out: torch.Tensor | None = None,
+                  out_channel_offset: int = 0, kernel=None, tile: int = 0) -> torch.Tensor:
+    """Depthwise NHWC conv (channel multiplier 1), ``act(conv + bias)``.
+
+    ``w_taps_c`` is ``[KH * KW, C]``, TF's ``[KH, KW, C, 1]`` filter flattened (give
+    ``kernel=(KH, KW)`` unless it is square); ``pad = (top, bottom, left, right)``.  With
+    ``out`` given, the result is written at channel offset ``out_channel_offset`` of it.
+    ``tile`` pins the 3x3 kernel's tile (``DWCONV_TILES``) or the generic kernel
+    (``DWCONV_GENERIC``): measurement and tests only."""
+    a = act_code(act)
+    if a not in (ACT_NONE, ACT_RELU, ACT_RELU6):
+        raise ValueError("dwconv2d_nhwc: act must be none, relu or relu6")
+    N, H, W, C = x.shape
+    taps, C2 = w_taps_c.shape
+    if kernel is None:
+        k = int(round(taps ** 0.5))
+        kernel = (k, k)
+    KH, KW = kernel
+    if KH * KW != taps or C2 != C:
+        raise ValueError(f"dwconv2d_nhwc: weights {tuple(w_taps_c.shape)} do not match a {KH}x{KW} filter over {C} "
+                         f"channels")
+    sh, sw = stride
+    pt, pb, pl, pr = pad
+    dh, dw = dilation
+    if not dwconv_eligible(C, KH, KW, stride, dilation) or min(pad) < 0:
+        raise ValueError(f"dwconv2d_nhwc: unsupported C={C}, {KH}x{KW}, stride {stride}, dilation {dilation}, "
+                         f"pad {pad}")
+    Ho, Wo = conv_out_hw(H, W, KH, KW, sh, sw, pt, pl, dh, dw, pb, pr)
+    if Ho < 1 or Wo < 1:
+        raise ValueError("dwconv2d_nhwc: empty output")
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=x.dtype if x.is_cuda else torch.float32, device=x.device)
+        out_channel_offset = 0
+    if out.dim() != 4 or out.shape[:3] != (N, Ho, Wo) or out_channel_offset < 0 \
+            or out_channel_offset + C > out.shape[3]:
+        raise ValueError(f"dwconv2d_nhwc: out {tuple(out.shape)} cannot hold [{N},{Ho},{Wo},{C}] at "
+                         f"offset {out_channel_offset}")
+    if x.is_cuda:
+        for t, n in ((x, "x"), (w_taps_c, "w"), (out, "out")):
+            _check(t, n, device=x.device)
+        if bias is not None:
+            _check(bias, "bias", torch.float32, x.device)
+            if bias.numel() != C:
+                raise ValueError("dwconv2d_nhwc: bias must have C elements")
+        if out.shape[3] % 8 or out_channel_offset % 8:
+            raise ValueError("dwconv2d_nhwc: output row pitch and channel offset must be multiples of 8")
+        _hip().dwconv_nhwc_bf16(x.data_ptr(), w_taps_c.data_ptr(), _ptr(bias), out.data_ptr(), N, H, W, C, Ho, Wo,
+                                KH, KW, sh, sw, dh, dw, pt, pl, a, out.shape[3], out_channel_offset, tile, _stream())
+        return out
+    xn = F.pad(x.float().permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    wn = w_taps_c.float().reshape(KH, KW, C).permute(2, 0, 1).unsqueeze(1)  # [C, 1, KH, KW]
+    y = F.conv2d(xn, wn, stride=(sh, sw), dilation=(dh, dw), groups=C)
+    if bias is not None:
+        y = y + bias.float().view(1, -1, 1, 1)
+    y = _apply_act_ref(y, a)
+    out[..., out_channel_offset:out_channel_offset + C] = y.permute(0, 2, 3, 1).to(out.dtype)
+    return out
+
+
 # ------------------------------------------------------------------------------ pooling
 def pool2d_nhwc(x: torch.Tensor, ksize, stride, pad=(0, 0, 0, 0), mode="max", out=None, out_channel_offset=0):
     N, H, W, C = x.shape
