@@ -95,8 +95,13 @@ class GraphBuilder:
     def mul(self, x, y, name=None) -> str:
         return self.op("Mul", [x, y], name=name)
 
-    def resize_bilinear(self, images, size, name=None, align_corners=False) -> str:
-        return self.op("ResizeBilinear", [images, size], name=name, align_corners=align_corners)
+    def resize_bilinear(self, images, size, name=None, align_corners=False, half_pixel_centers=None) -> str:
+        return self.op("ResizeBilinear", [images, size], name=name, align_corners=align_corners,
+                       half_pixel_centers=half_pixel_centers)
+
+    def argmax(self, x, axis, output_type="INT64", name=None) -> str:
+        a = self.constant(f"{(name or 'ArgMax')}/dimension", np.asarray(axis, dtype=np.int32))
+        return self.op("ArgMax", [x, a], name=name, output_type=DataType.of(output_type))
 
     def expand_dims(self, x, dim, name=None) -> str:
         return self.op("ExpandDims", [x, dim], name=name)

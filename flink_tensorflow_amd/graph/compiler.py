@@ -15,6 +15,9 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``DepthwiseConv2dNative → [BiasAdd | FusedBatchNorm]* → [Relu|Relu6]`` → one launch of
      the depthwise kernel (3x3 register-tiled or generic), BN folded into the per-channel
      filter; a residual ``Add`` behind it stays an elementwise step;
+   * ``ResizeBilinear`` of an activation → the bilinear resize kernel (it writes concat
+     slots); ``[ResizeBilinear] → ArgMax(channels) → [Cast]`` → one fused resize + ArgMax
+     launch that never stores the resized tensor (kernels/resize.hip);
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -411,6 +414,10 @@ class CompiledFunction(TransformerLowering, ConvLowering):
             return self._lower_matmul(node)
         if op == "Cast" and self._try_preprocess(node):
             return
+        if op == "ResizeBilinear":
+            return self._lower_resize(node)
+        if op == "ArgMax":
+            return self._lower_argmax(node)
         if op in ("MaxPool", "AvgPool"):
             return self._lower_pool(node)
         if op == "Mean":
@@ -664,10 +671,98 @@ class CompiledFunction(TransformerLowering, ConvLowering):
             self.vals[(n.name, 0)] = out
         return True
 
+    # ---- bilinear resize / ArgMax (dense prediction heads: kernels/resize.hip)
+    def _resize_source_ok(self, x: Val | None, pitch8: bool) -> bool:
+        """``x`` is a 4-D activation the resize kernels can read: bf16 (a channel-padded
+        buffer included when ``pitch8`` only asks for a pitch of 8-channel vectors), fed fp32
+        or fp8 (both through ``_as_bf16``)."""
+        if x is None or x.is_const or len(x.shape) != 4 or x.pre_cfg is not None or x.rows is not None:
+            return False
+        if x.dtype == torch.bfloat16 and pitch8:
+            return (x.phys_c or x.shape[-1]) % 8 == 0
+        if x.dtype == torch.bfloat16:
+            return not x.phys_c and x.shape[-1] % 8 == 0
+        return (x.dtype == torch.float32 or x.qscale is not None) and not x.phys_c and x.shape[-1] % 8 == 0
+
+    def _argmax_ok(self, node: Node, shape: tuple) -> bool:
+        """An ``ArgMax`` over the last axis of a 4-D value with at most 256 channels."""
+        av = self._get(node.inputs[1])
+        if av is None or not av.is_const or len(shape) != 4 or not 1 <= shape[-1] <= 256:
+            return False
+        return int(av.const.reshape(-1)[0].item()) % 4 == 3 and \
+            node.attr("output_type", DataType.INT64).torch in (torch.int32, torch.int64)
+
+    def _lower_resize(self, node: Node):
+        """``ResizeBilinear`` of an activation as one ``resize`` step (it can write a concat
+        slot).  When its only consumer is a lowerable ``ArgMax`` and it is not fetched it
+        emits nothing: the ``ArgMax`` interpolates on the fly (``_lower_argmax``)."""
+        x = self._in(node, 0)
+        sv = self._get(node.inputs[1])
+        if sv is None or not sv.is_const or x.is_const or len(x.shape) != 4:
+            return self._lower_glue(node)
+        Ho, Wo = (int(v) for v in sv.const.reshape(-1).tolist())
+        N, _, _, C = x.shape
+        geo = (bool(node.attr("align_corners", False)), bool(node.attr("half_pixel_centers", False)))
+        if Ho < 1 or Wo < 1:
+            return self._lower_glue(node)
+        nxt = self._single_consumer(node.name)
+        if nxt is not None and nxt.op == "ArgMax" and nxt.inputs[0][0] == node.name \
+                and self._argmax_ok(nxt, (N, Ho, Wo, C)) and self._resize_source_ok(x, pitch8=True):
+            out = self._new((N, Ho, Wo, C))
+            out.resize_of = (x, *geo)  # no step, no buffer: read only by that ArgMax
+            self.vals[(node.name, 0)] = out
+            return
+        # a channel-padded bf16 producer (a conv of e.g. 21 classes) is resized at its padded
+        # width: the padding is zeros and stays zeros, the result is padded the same way
+        phys = x.phys_c if x.dtype == torch.bfloat16 and x.phys_c and x.phys_c % 8 == 0 else None
+        if not self._resize_source_ok(x, pitch8=phys is not None):
+            return self._lower_glue(node)
+        xin = self._as_bf16(x, node.name)
+        out = self._new((N, Ho, Wo, C), phys_c=phys)
+        cr = phys or C
+
+        def run(xin=xin, out=out):
+            K.resize_bilinear_nhwc(xin.buf, (Ho, Wo), geo[0], geo[1], out=_target(out), out_channel_offset=_coff(out),
+                                   channels=cr)
+
+        self._emit(node.name, "resize", run, [xin], [out])
+        self.vals[(node.name, 0)] = out
+
+    def _lower_argmax(self, node: Node):
+        """``ArgMax`` over the channels of a 4-D value as one ``resize_argmax`` step: fused
+        with the ``ResizeBilinear`` it absorbed, else with identity geometry.  A channel-padded
+        producer is read in place (the kernel takes the logical ``C``); a ``Cast`` to an
+        integer type that is the only consumer becomes the store type."""
+        x = self._in(node, 0)
+        if x.is_const or not self._argmax_ok(node, tuple(x.shape)):
+            return self._lower_glue(node)
+        src, align, half = getattr(x, "resize_of", (x, False, False))
+        if not self._resize_source_ok(src, pitch8=True):
+            return self._lower_glue(node)
+        N, Ho, Wo, C = x.shape
+        dtype = node.attr("output_type", DataType.INT64).torch
+        cast = self._single_consumer(node.name)
+        if cast is not None and cast.op == "Cast" and \
+                DataType.of(cast.attr("DstT")).torch in (torch.uint8, torch.int32, torch.int64):
+            dtype = DataType.of(cast.attr("DstT")).torch  # C <= 256: every label fits a byte
+            self._fused.add(cast.name)
+        else:
+            cast = None
+        xin = self._as_bf16(src, node.name)
+        out = self._new((N, Ho, Wo), dtype)
+
+        def run(xin=xin, out=out):
+            K.resize_argmax_nhwc(xin.buf, (Ho, Wo), align, half, channels=C, out=out.buf)
+
+        self._emit(node.name, "resize_argmax", run, [xin], [out], {"fused_resize": src is not x})
+        self.vals[(node.name, 0)] = out
+        if cast is not None:
+            self.vals[(cast.name, 0)] = out
+
     # ---- pooling / reductions / softmax
     def _lower_pool(self, node: Node):
         x = self._in(node, 0)
-        if node.attr("data_format", "NHWC") != "NHWC" or (x.phys_c or x.shape[-1]) % 8:
+        if node.attr("data_format", "NHWC") != "NHWC" or x.phys_c or x.shape[-1] % 8:
             return self._lower_glue(node)
         k = node.attr("ksize")
         s = node.attr("strides")
@@ -791,7 +886,10 @@ class CompiledFunction(TransformerLowering, ConvLowering):
         out = self._new(tuple(shape), torch.uint8 if fp8 else torch.bfloat16)
         if fp8:
             out.qscale = self._qscale(node.name)
+        # one storage format per buffer: all fp8 at the concat's scale, or all bf16 (an fp8
+        # plan's resize or depthwise branch next to fp8 convs is joined by the bf16 copy below)
         stride_write = (axis == len(shape) - 1 and len(shape) == 4
+                        and (fp8 or not any(v.qscale is not None for v in ins))
                         and all(self._concat_writable(v, node.inputs[i][0], node.name) for i, v in enumerate(ins)))
         if stride_write:
             off = 0
@@ -806,16 +904,17 @@ class CompiledFunction(TransformerLowering, ConvLowering):
             ins = [self._as_bf16(v, f"{node.name}/in{i}") for i, v in enumerate(ins)]
 
         def run(ins=ins, out=out, axis=axis):
-            torch.cat([v.buf for v in ins], dim=axis, out=out.buf)
+            torch.cat([_view(v) for v in ins], dim=axis, out=out.buf)
 
         self._emit(node.name, "concat", run, ins, [out])
         self.vals[(node.name, 0)] = out
 
     def _concat_writable(self, v: Val, src_node: str, concat_node: str) -> bool:
-        # produced by exactly one conv/pool step (which can write at a channel offset),
+        # produced by exactly one conv/pool/resize step (which can write at a channel offset),
         # consumed by nothing but this concat, and not fetched
         prods = [s for s in self.steps if any(o is v for o in s.outputs)]
-        if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8") or v.concat_slot is not None \
+        if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize") \
+                or v.concat_slot is not None \
                 or (len(prods[0].outputs) != 1 and not prods[0].meta.get("multi_out")):
             return False
         if v.alias_of is not None or v.phys_c:

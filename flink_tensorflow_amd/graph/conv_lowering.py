@@ -231,8 +231,6 @@ class ConvLowering:
             pt = pb = pl = pr = 0
         else:
             return None
-        if Cout % 8:
-            return None
         Ho = (H + pt + pb - ((KH - 1) * dh + 1)) // sh + 1
         Wo = (W + pl + pr - ((KW - 1) * dw + 1)) // sw + 1
         return w, (sh, sw), (dh, dw), (pt, pb, pl, pr), (Ho, Wo)
@@ -251,12 +249,23 @@ class ConvLowering:
         if scale is not None:
             w = w * scale
         KH, KW, Cin, Cout = w.shape
+        n_pad = -(-Cout // 8) * 8
+        if n_pad != Cout:
+            # e.g. 21 classes: zero filters and biases up to a multiple of 8, as _lower_matmul
+            # pads GEMM columns; the output value keeps its logical shape over a padded buffer
+            # (``phys_c``).  Only the plain chain: a residual would need the same padding.
+            if residual is not None:
+                return self._lower_glue(node)
+            w = torch.nn.functional.pad(w, (0, n_pad - Cout))
+            bias = torch.nn.functional.pad(bias if bias is not None else torch.zeros(Cout), (0, n_pad - Cout))
         if self.precision == "fp8" and self._conv_fp8_ok(node, x, Cin, Cout, residual, act):
             return self._lower_conv_fp8(node, x, w, bias, act, last, absorbed, (KH, KW, Cin, Cout), stride, pads, dil,
                                         (x.shape[0], *out_hw))
-        c = self._prepare_conv(node, x, w, bias, residual, act, last, absorbed, stride, pads, dil, out_hw)
+        c = self._prepare_conv(node, x, w, bias, residual, act, last, absorbed, stride, pads, dil, out_hw, Cout)
         # 3./4. the kernel; a residual 1x1 conv first tries the fusions that need plan state
         impl = select_conv_kernel(c.site)
+        if n_pad != Cout and impl == "dconv":
+            impl = "igemm"  # the direct conv's pool / preprocess fusions assume an unpadded output
         if impl in AFTER_FUSIONS and self._fuse_residual_conv(c):
             return
         # 5. one launch step
@@ -310,9 +319,13 @@ class ConvLowering:
         self._emit(node.name, "dwconv", run, [xin], [out], {"impl": K.dwconv_impl(KH, KW, stride, dil)})
         self._finish_conv(last, absorbed, out)
 
-    def _prepare_conv(self, node, x, w, bias, residual, act, last, absorbed, stride, pads, dil, out_hw) -> _ConvJob:
-        """Weights, input and output values of a bf16 conv chain, and its ``ConvSite``."""
+    def _prepare_conv(self, node, x, w, bias, residual, act, last, absorbed, stride, pads, dil, out_hw,
+                      cout_logical: int | None = None) -> _ConvJob:
+        """Weights, input and output values of a bf16 conv chain, and its ``ConvSite``.  With
+        ``cout_logical`` below the filter's (zero-padded) output channels, the output value has
+        that many channels over a buffer of the padded width."""
         KH, KW, Cin, Cout = w.shape
+        padded = cout_logical is not None and cout_logical != Cout
         N, H, W, C = x.shape
         s2d = self._s2d_ok(x, node, C, *stride, *dil, pads[0], pads[2], H, W)
         if s2d:
@@ -332,9 +345,9 @@ class ConvLowering:
         w_dev = self._dev(w_ohwi, torch.bfloat16)
         b_dev = self._dev(bias, torch.float32) if bias is not None else None
         self.params += [w_dev] + ([b_dev] if b_dev is not None else [])
-        out = self._new((N, *out_hw, Cout))
+        out = self._new((N, *out_hw, cout_logical if padded else Cout), phys_c=Cout if padded else None)
         kernel = tuple(w_ohwi.shape[1:3])
-        if (self.precision == "fp8" and residual is None and act in _PLAIN_ACTS and Cout % 16 == 0
+        if (not padded and self.precision == "fp8" and residual is None and act in _PLAIN_ACTS and Cout % 16 == 0
                 and self._fp8_consumers_ok(last.name) and self._qscale(last.name) is not None
                 and _dconv_ok(self.device.type == "cuda", cin_pad, kernel, stride, dil, 2, False, act)):
             # bf16 direct-conv layer (the RGB stem) feeding fp8 consumers: emit e4m3 directly

@@ -1,5 +1,6 @@
 """Model zoo.  The model classes load lazily: importing the package pulls in no compiler."""
-_EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "mobilenet"}
+_EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "mobilenet",
+            "DeepLabV3Model": "image_classifier", "deeplab_v3_graph_def": "deeplab"}
 
 __all__ = sorted(_EXPORTS)
 

@@ -148,7 +148,7 @@ class ImageClassifierModel(GenericModel, BatchedGpuModel):
 
     def submit(self, records, ingest_ts, tags):
         if self._runner is None:  # host fallback: synchronous interpreter run
-            out = self.label(records)
+            out = self._sync_results(records)
             import time
 
             return [(out, tags, time.perf_counter() - np.asarray(ingest_ts))]
@@ -169,9 +169,20 @@ class ImageClassifierModel(GenericModel, BatchedGpuModel):
         return [self._results(b) for b in self._runner.drain()] if self._runner is not None else []
 
     # ------------------------------------------------------------------ synchronous API
+    def _sync_results(self, records):
+        """What the host fallback of ``submit`` returns per record: the synchronous API."""
+        return self.label(records)
+
     def label(self, images) -> list[list[tuple[float, str]]]:
         """Top-k ``(probability, label)`` per image (``InceptionModel.label`` +
         ``toTextLabels``)."""
+        vals, idxs = self._run_sync(images)
+        return [[(float(v), self.label_of(int(i))) for v, i in zip(vr, ir)]
+                for vr, ir in zip(vals.tolist(), idxs.tolist())]
+
+    def _run_sync(self, images) -> list[torch.Tensor]:
+        """The fetches for ``images`` as host tensors, one row per image: through the plan of
+        the smallest bucket that holds them when open on a GPU, else the interpreter."""
         arrs = [self._as_array(r) for r in images]
         if any(isinstance(a, (bytes, bytearray)) for a in arrs):
             from ...graph.ops_io import decode_jpegs
@@ -188,12 +199,9 @@ class ImageClassifierModel(GenericModel, BatchedGpuModel):
             if b is not None:
                 buf = np.zeros((b, *arrs.shape[1:]), dtype=np.uint8)
                 buf[:n] = arrs
-                vals, idxs = self._plans[b]({self.feed: torch.from_numpy(buf).to(sess.device)})
-                vals, idxs = vals[:n].cpu(), idxs[:n].cpu()
-                return [[(float(v), self.label_of(int(i))) for v, i in zip(vr, ir)]
-                        for vr, ir in zip(vals.tolist(), idxs.tolist())]
-        vals, idxs = sess.run(self.fetches, {self.feed: torch.from_numpy(arrs)})
-        return [[(float(v), self.label_of(int(i))) for v, i in zip(vr, ir)] for vr, ir in zip(vals.tolist(), idxs.tolist())]
+                outs = self._plans[b]({self.feed: torch.from_numpy(buf).to(sess.device)})
+                return [o[:n].cpu() for o in outs]
+        return [torch.as_tensor(o) for o in sess.run(self.fetches, {self.feed: torch.from_numpy(arrs)})]
 
 
 class ResNet50Model(ImageClassifierModel):
@@ -228,6 +236,42 @@ class MobileNetV1Model(ImageClassifierModel):
 
         return mobilenet_v1_graph_def(alpha=self.alpha, num_classes=self.num_classes, seed=self.seed,
                                       image_hw=self.image_hw, out_hw=self.out_hw, top_k=self.top_k)
+
+
+class DeepLabV3Model(ImageClassifierModel):
+    """DeepLab-v3 on the MobileNet-V1 backbone (random-init frozen graph): semantic
+    segmentation.  The plan is strict: atrous convs on the implicit GEMM, the ASPP
+    image-pooling branch on the resize kernel, the logits upsample and the ArgMax as one fused
+    launch that stores the uint8 label map.  Results are ``[H, W]`` uint8 maps, one per image,
+    from ``segment`` and from the batched ``submit`` / ``poll`` / ``drain`` path alike."""
+
+    def __init__(self, image_hw=(513, 513), buckets=(8, 32), seed: int = 0, device=None, alpha: float = 1.0,
+                 crop_hw=(513, 513), num_classes: int = 21, output_stride: int = 16, atrous_rates=(6, 12, 18),
+                 fetches=("label_map:0",), **kw):
+        self.seed = seed
+        self.alpha = alpha
+        self.crop_hw = tuple(crop_hw)
+        self.num_classes = num_classes
+        self.output_stride = output_stride
+        self.atrous_rates = tuple(atrous_rates)
+        super().__init__(self._make_graph, image_hw, buckets, 1, device=device, fetches=fetches, **kw)
+
+    def _make_graph(self) -> GraphDef:
+        from .deeplab import deeplab_v3_graph_def
+
+        return deeplab_v3_graph_def(alpha=self.alpha, num_classes=self.num_classes, image_hw=self.image_hw,
+                                    crop_hw=self.crop_hw, output_stride=self.output_stride,
+                                    atrous_rates=self.atrous_rates, seed=self.seed)
+
+    def segment(self, images) -> list[np.ndarray]:
+        """One ``[H, W]`` uint8 label map per image (synchronous)."""
+        return list(self._run_sync(images)[0].numpy())
+
+    def _sync_results(self, records):
+        return self.segment(records)
+
+    def _results(self, br):
+        return list(br.outputs[0][: br.n].numpy()), br.tags, br.latencies
 
 
 class InceptionV3Model(ImageClassifierModel):

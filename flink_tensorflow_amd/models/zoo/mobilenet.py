@@ -10,8 +10,9 @@ every BatchNorm into its conv, runs the depthwise layers on ``kernels/dwconv.hip
 stem and pointwise layers on the implicit GEMM with its Relu6 epilogue.
 
 Channel counts are ``alpha``-scaled and rounded to multiples of 8.  TF-slim's 1001-way
-1x1-conv classifier is replaced by ``Mean → MatMul`` (the conv kernels want a multiple of 8
-output channels).
+1x1-conv classifier is replaced by ``Mean → MatMul``, as newer exports do (a conv whose output
+channels are no multiple of 8 lowers too: the compiler zero-pads its filters to the next
+multiple and the consumers read the logical columns).
 
 Tensor names: ``images`` (uint8 [N,H,W,3]), ``normalized``, ``logits``, ``probs``, ``top_k``
 (``top_k:0`` values, ``top_k:1`` indices).

@@ -873,6 +873,96 @@ def dwconv2d_nhwc(x: torch.Tensor, w_taps_c: torch.Tensor, bias: torch.Tensor | 
     return out
 
 
+# ------------------------------------------------------------------------------ bilinear resize / ArgMax
+# kernel of ``resize_argmax_nhwc`` (kernels/resize.hip); 0 = the launcher's choice
+RESIZE_ARGMAX_PATHS = {"staged": 1, "simple": -1}
+_LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def _resize_args(name: str, x: torch.Tensor, out_hw, channels):
+    if x.dim() != 4:
+        raise ValueError(f"{name}: x must be [N, H, W, C], got {tuple(x.shape)}")
+    N, H, W, ldx = x.shape
+    C = ldx if channels is None else int(channels)
+    Ho, Wo = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if min(N, H, W, ldx) < 1 or Ho < 1 or Wo < 1:
+        raise ValueError(f"{name}: empty input {tuple(x.shape)} or output {(Ho, Wo)}")
+    if ldx % 8:
+        raise ValueError(f"{name}: the pixel pitch {ldx} of x must be a multiple of 8")
+    if not 1 <= C <= ldx:
+        raise ValueError(f"{name}: channels={C} outside 1..{ldx}")
+    return N, H, W, ldx, C, Ho, Wo
+
+
+def resize_bilinear_nhwc(x: torch.Tensor, out_hw, align_corners: bool = False, half_pixel_centers: bool = False,
+                         out: torch.Tensor | None = None, out_channel_offset: int = 0,
+                         channels: int | None = None) -> torch.Tensor:
+    """TF ``ResizeBilinear`` of an NHWC activation (``graph/ops_nn.py:resize_bilinear_tf`` is
+    the definition): fp32 lerps, one rounding.  ``channels`` is the logical ``C`` when
+    ``x.shape[-1]`` is a padded pitch.  With ``out`` given, the ``C`` result channels are
+    written at channel offset ``out_channel_offset`` of it (a concat slot)."""
+    N, H, W, ldx, C, Ho, Wo = _resize_args("resize_bilinear_nhwc", x, out_hw, channels)
+    if C % 8:
+        raise ValueError(f"resize_bilinear_nhwc: C={C} must be a multiple of 8")
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+        out_channel_offset = 0
+    if out.dim() != 4 or tuple(out.shape[:3]) != (N, Ho, Wo) or out_channel_offset < 0 \
+            or out_channel_offset + C > out.shape[3]:
+        raise ValueError(f"resize_bilinear_nhwc: out {tuple(out.shape)} cannot hold [{N},{Ho},{Wo},{C}] at "
+                         f"offset {out_channel_offset}")
+    if out.shape[3] % 8 or out_channel_offset % 8:
+        raise ValueError("resize_bilinear_nhwc: output row pitch and channel offset must be multiples of 8")
+    if x.is_cuda:
+        _check(x, "x", device=x.device)
+        _check(out, "out", device=x.device)
+        _hip().resize_bilinear_nhwc_bf16(x.data_ptr(), out.data_ptr(), N, H, W, C, Ho, Wo, ldx, out.shape[3],
+                                         out_channel_offset, bool(align_corners), bool(half_pixel_centers), _stream())
+        return out
+    from ..graph.ops_nn import resize_bilinear_tf
+
+    y = resize_bilinear_tf(x[..., :C], Ho, Wo, align_corners, half_pixel_centers)
+    out[..., out_channel_offset:out_channel_offset + C] = y.to(out.dtype)
+    return out
+
+
+def resize_argmax_nhwc(x: torch.Tensor, out_hw=None, align_corners: bool = False, half_pixel_centers: bool = False,
+                       channels: int | None = None, out: torch.Tensor | None = None, out_dtype=torch.int32,
+                       path: int = 0) -> torch.Tensor:
+    """Channel ArgMax of the bilinearly resized logits ``x`` ``[N, H, W, ldx]`` as a
+    ``[N, Ho, Wo]`` label map (uint8, int32 or int64); the resized tensor is never stored.
+    ``channels`` is the logical ``C <= 256`` when ``x.shape[-1]`` is a padded pitch: the
+    padding columns are ignored.  Values are interpolated and compared in fp32, ties go to
+    the lowest channel.  Without ``out_hw`` it is a plain ArgMax over the last axis.
+    ``path`` pins the kernel (``RESIZE_ARGMAX_PATHS``): measurement and tests only."""
+    N, H, W, ldx, C, Ho, Wo = _resize_args("resize_argmax_nhwc", x, out_hw, channels)
+    if C > 256:
+        raise ValueError(f"resize_argmax_nhwc: C={C} exceeds 256")
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in _LABEL_BYTES:
+        raise TypeError(f"resize_argmax_nhwc: labels are uint8, int32 or int64, not {out_dtype}")
+    if path not in (0, 1, -1):
+        raise ValueError(f"resize_argmax_nhwc: path {path!r} is not one of 0, 1, -1")
+    if out is None:
+        out = torch.empty((N, Ho, Wo), dtype=out_dtype, device=x.device)
+    if tuple(out.shape) != (N, Ho, Wo):
+        raise ValueError(f"resize_argmax_nhwc: out {tuple(out.shape)} is not [{N},{Ho},{Wo}]")
+    if x.is_cuda:
+        _check(x, "x", device=x.device)
+        _check(out, "out", out_dtype, x.device)
+        _hip().resize_argmax_nhwc_bf16(x.data_ptr(), out.data_ptr(), N, H, W, C, Ho, Wo, ldx, _LABEL_BYTES[out_dtype],
+                                       bool(align_corners), bool(half_pixel_centers), path, _stream())
+        return out
+    from ..graph.ops_nn import resize_bilinear_tf
+
+    y = resize_bilinear_tf(x[..., :C].float(), Ho, Wo, align_corners, half_pixel_centers)
+    # the first of the largest: torch.argmax does not promise which of several it returns
+    first = torch.where(y == y.amax(-1, keepdim=True), torch.arange(C), C).amin(-1)
+    out.copy_(first.to(out.dtype))
+    return out
+
+
 # ------------------------------------------------------------------------------ pooling
 def pool2d_nhwc(x: torch.Tensor, ksize, stride, pad=(0, 0, 0, 0), mode="max", out=None, out_channel_offset=0):
     N, H, W, C = x.shape
