@@ -168,6 +168,70 @@ class GraphBuilder:
         a = self.constant(f"{(name or 'concat')}/axis", np.asarray(axis, dtype=np.int32))
         return self.op("ConcatV2", list(xs) + [a], name=name, N=len(xs))
 
+    def sigmoid(self, x, name=None) -> str:
+        return self.op("Sigmoid", [x], name=name)
+
+    def exp(self, x, name=None) -> str:
+        return self.op("Exp", [x], name=name)
+
+    def strided_slice(self, x, begin, end, strides=None, name=None, begin_mask=0, end_mask=0, shrink_axis_mask=0) -> str:
+        """``x[begin:end:strides]`` over the leading ``len(begin)`` axes; bit ``d`` of
+        ``begin_mask`` / ``end_mask`` opens that side of axis ``d``."""
+        nm = name or "StridedSlice"
+        strides = [1] * len(begin) if strides is None else strides
+        b, e, s = (self.constant(f"{nm}/{k}", np.asarray(v, dtype=np.int32))
+                   for k, v in (("begin", begin), ("end", end), ("strides", strides)))
+        return self.op("StridedSlice", [x, b, e, s], name=name, begin_mask=int(begin_mask), end_mask=int(end_mask),
+                       ellipsis_mask=0, new_axis_mask=0, shrink_axis_mask=int(shrink_axis_mask), Index=DataType.INT32)
+
+    def last_axis_slice(self, x, lo, hi, rank=3, name=None) -> str:
+        """``x[..., lo:hi]`` of a rank-``rank`` tensor as one ``StridedSlice``."""
+        lead = (1 << (rank - 1)) - 1
+        return self.strided_slice(x, [0] * (rank - 1) + [lo], [0] * (rank - 1) + [hi], name=name, begin_mask=lead,
+                                  end_mask=lead)
+
+    def decode_boxes(self, encodings, anchors_yxhw, scales=(10.0, 10.0, 5.0, 5.0), name="decode_boxes") -> str:
+        """SSD box decoding of ``encodings`` ``[B, N, 4]`` = (ty, tx, th, tw) against the anchor
+        table ``anchors_yxhw`` ``[N, 4]`` = (yc, xc, h, w), as ``[B, N, 1, 4]`` corner boxes (the
+        ``boxes`` input of ``combined_nms``).  Emitted in primitive ops in one fixed form, which
+        ``graph/detection_lowering.py`` documents and recognises; constants are split per
+        (y, x) pair so that every op is a plain broadcast."""
+        a = np.asarray(anchors_yxhw, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 4 or len(scales) != 4:
+            raise ValueError("decode_boxes: anchors must be [N, 4] and scales four numbers")
+        inv = (np.float32(1) / np.asarray(scales, dtype=np.float32)).astype(np.float32)
+        with self.name_scope(name):
+            t_yx = self.last_axis_slice(encodings, 0, 2, name="t_yx")
+            t_hw = self.last_axis_slice(encodings, 2, 4, name="t_hw")
+            a_yx = self.constant("anchors_yx", np.ascontiguousarray(a[:, 0:2]))
+            a_hw = self.constant("anchors_hw", np.ascontiguousarray(a[:, 2:4]))
+            c = self.mul(t_yx, self.constant("inv_scale_yx", inv[0:2]), name="scaled_yx")
+            c = self.mul(c, a_hw, name="offset_yx")
+            c = self.add(c, a_yx, name="centre")
+            s = self.mul(t_hw, self.constant("inv_scale_hw", inv[2:4]), name="scaled_hw")
+            s = self.exp(s, name="Exp")
+            s = self.mul(s, a_hw, name="size")
+            half = self.mul(s, self.constant("half", np.float32(0.5)), name="half_size")
+            lo = self.sub(c, half, name="min_corner")
+            hi = self.add(c, half, name="max_corner")
+            boxes = self.concat([lo, hi], -1, name="corners")
+            return self.expand_dims(boxes, self.constant("boxes/dim", np.asarray(2, dtype=np.int32)), name="boxes")
+
+    def combined_nms(self, boxes, scores, max_per_class, max_total, iou_threshold=0.5, score_threshold=0.0,
+                     pad_per_class=False, clip_boxes=True, name=None) -> str:
+        """``CombinedNonMaxSuppression``; outputs ``:0`` boxes, ``:1`` scores, ``:2`` classes,
+        ``:3`` valid_detections.  A scalar argument may be a tensor name instead of a number."""
+        nm = name or "CombinedNonMaxSuppression"
+
+        def scalar(key, v, dt):
+            return v if isinstance(v, str) else self.constant(f"{nm}/{key}", np.asarray(v, dtype=dt))
+
+        return self.op("CombinedNonMaxSuppression",
+                       [boxes, scores, scalar("max_output_size_per_class", max_per_class, np.int32),
+                        scalar("max_total_size", max_total, np.int32), scalar("iou_threshold", iou_threshold, np.float32),
+                        scalar("score_threshold", score_threshold, np.float32)],
+                       name=name, pad_per_class=bool(pad_per_class), clip_boxes=bool(clip_boxes))
+
     def top_k(self, x, k, name=None) -> str:
         kk = self.constant(f"{(name or 'TopKV2')}/k", np.asarray(k, dtype=np.int32))
         return self.op("TopKV2", [x, kk], name=name, sorted=True)

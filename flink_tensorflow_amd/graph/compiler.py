@@ -18,6 +18,9 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``ResizeBilinear`` of an activation → the bilinear resize kernel (it writes concat
      slots); ``[ResizeBilinear] → ArgMax(channels) → [Cast]`` → one fused resize + ArgMax
      launch that never stores the resized tensor (kernels/resize.hip);
+   * ``[decode_boxes subgraph] + [last-axis score slice] → CombinedNonMaxSuppression`` → one
+     ``nms`` step: box decoding, per-class greedy NMS and the top-T merge
+     (kernels/detection.hip, ``detection_lowering.py``);
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -31,11 +34,12 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is four modules: ``plan.py`` (``Val``, ``Step``, ``CompileError`` and the
+The compiler is five modules: ``plan.py`` (``Val``, ``Step``, ``CompileError`` and the
 helpers that map a value to its buffer; re-exported here), ``conv_lowering.py`` (the
 ``ConvLowering`` mixin: Conv2D chains, the pure kernel choice ``select_conv_kernel`` and the
 block-tail post-passes), ``transformer_lowering.py`` (the ``TransformerLowering`` mixin: BERT
-patterns, token packing) and this one (pruning, folding, MatMul / pooling / concat / glue
+patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering`` mixin: box
+decoding + NMS) and this one (pruning, folding, MatMul / pooling / concat / glue
 lowering, memory planning, the batch-slice chain, capture and replay).
 
 Activations are bf16 NHWC on device; fetched outputs are cast back to the graph dtype.
@@ -66,6 +70,7 @@ from ..types.tensor import StringTensor
 from ..utils import tracing
 from . import ops_core  # noqa: F401
 from .conv_lowering import _ACTS, ConvLowering
+from .detection_lowering import _UNPADDED_NMS, DetectionLowering
 from .graph import Graph, Node
 from .op_registry import OpContext, lookup
 from .ops_nn import same_pads
@@ -92,7 +97,7 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, ConvLowering):
+class CompiledFunction(TransformerLowering, DetectionLowering, ConvLowering):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -187,6 +192,7 @@ class CompiledFunction(TransformerLowering, ConvLowering):
                 self.cons.setdefault(s, []).append(n)
         self._groups = {}
         self._prematch_transformer()  # layer_norm / attention / embedding patterns (BERT graphs)
+        self._prematch_detection()  # the box-decode subgraph in front of a CombinedNonMaxSuppression
         if self.token_cap is not None:
             self._setup_packing()  # CompileError when the graph cannot run token-packed
         for f in fed:
@@ -418,6 +424,10 @@ class CompiledFunction(TransformerLowering, ConvLowering):
             return self._lower_resize(node)
         if op == "ArgMax":
             return self._lower_argmax(node)
+        if op == "CombinedNonMaxSuppression":
+            return self._lower_combined_nms(node)
+        if op in _UNPADDED_NMS:
+            return self._lower_unpadded_nms(node)
         if op in ("MaxPool", "AvgPool"):
             return self._lower_pool(node)
         if op == "Mean":
@@ -434,6 +444,8 @@ class CompiledFunction(TransformerLowering, ConvLowering):
             return
         if op == "Reshape":
             return self._lower_reshape(node)
+        if op in ("StridedSlice", "Slice") and self._lower_score_slice(node):
+            return
         if op == "StridedSlice" and self._lower_strided_slice(node):
             return
         if op in ("Squeeze", "ExpandDims") and self._lower_squeeze_like(node):
@@ -861,11 +873,22 @@ class CompiledFunction(TransformerLowering, ConvLowering):
     def _lower_reshape(self, node: Node):
         x = self._in(node, 0)
         sv = self._get(node.inputs[1])
-        if sv is None or not sv.is_const or x.phys_c:
+        if sv is None or not sv.is_const or (x.phys_c and (x.is_const or x.rows is not None or x.buf_shape)):
             return self._lower_glue(node)
         shape = [int(v) for v in sv.const.reshape(-1).tolist()]
         if x.rows is not None:
             return self._reshape_rows(node, x, shape)
+        if x.phys_c:
+            # a channel-padded conv output (an SSD head of 3 x 4 = 12 or 3 x 91 = 273 channels):
+            # compact the logical columns first, as the StridedSlice copy does, then alias
+            packed = self._new(x.shape, x.dtype)
+            packed.qscale = x.qscale
+
+            def run(x=x, packed=packed):
+                packed.buf.copy_(_view(x))
+
+            self._emit(node.name, "copy", run, [x], [packed])
+            x = packed
         n = int(np.prod(x.shape))
         if -1 in shape:
             i = shape.index(-1)

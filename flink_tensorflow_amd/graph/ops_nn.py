@@ -224,3 +224,163 @@ def _resize_nn(ctx, node, x, size):
 @register("L2Normalize")
 def _l2n(ctx, node, x):
     return (F.normalize(x, dim=-1),)
+
+
+# ------------------------------------------------------------------------------ detection: box decode + NMS
+# The semantic reference of the detection heads (TF's ``non_max_suppression_op.cc``), with what
+# TF leaves open pinned down.  ``kernels/detection.hip`` computes the same thing operation for
+# operation in fp32; ``K.combined_nms`` runs these routines on host tensors.
+#
+# * Per image and class the candidates are the boxes with ``score > score_threshold`` (a NaN
+#   never passes), visited in descending score, **equal scores lower box index first** (TF's
+#   priority queue leaves ties open).  A candidate is kept unless its IoU with a box already
+#   kept for that class is ``> iou_threshold``; selection stops at ``min(max_per_class, N)``.
+# * IoU is taken on the canonicalised corners (min / max of the two y and of the two x values),
+#   every operation rounded to fp32: ``area = (y2 - y1) * (x2 - x1)``, ``inter = max(0, min(y2) -
+#   max(y1)) * max(0, min(x2) - max(x1))``, ``iou = inter / ((area_a + area_b) - inter)``, and 0
+#   when either area is <= 0.
+# * The kept boxes of all classes are merged in descending score, **equal scores lower class
+#   first, then lower box index**, and the first ``T`` are taken.
+def decode_boxes_yxhw(enc, anchors, scales):
+    """SSD box decoding in fp32, every operation rounded, in this order (``scales`` are the
+    four *reciprocal* scale factors ``s0..s3``, ``anchors`` is ``[N, 4]`` = (yc, xc, h, w))::
+
+        cy = (ty * s0) * ha + yca        cx = (tx * s1) * wa + xca
+        h  = exp(th * s2) * ha           w  = exp(tw * s3) * wa
+        box = (cy - 0.5 * h, cx - 0.5 * w, cy + 0.5 * h, cx + 0.5 * w)
+
+    ``enc`` is ``[..., N, 4]`` = (ty, tx, th, tw); the result has its shape, fp32."""
+    enc = torch.as_tensor(enc).float()
+    a = torch.as_tensor(anchors).float()
+    s = torch.as_tensor(scales, dtype=torch.float32)
+    c = enc[..., 0:2] * s[0:2] * a[:, 2:4] + a[:, 0:2]
+    hw = torch.exp(enc[..., 2:4] * s[2:4]) * a[:, 2:4]
+    half = hw * 0.5
+    return torch.cat([c - half, c + half], dim=-1)
+
+
+def _nms_class_np(boxes, scores, max_out, iou_thr, score_thr):
+    """Greedy NMS of one class: ``boxes`` [N, 4] and ``scores`` [N] fp32 numpy arrays; the kept
+    box indices in selection order."""
+    import numpy as np
+
+    cand = np.nonzero(scores > score_thr)[0]
+    order = cand[np.argsort(-scores[cand], kind="stable")]  # equal scores: lower index first
+    y1, y2 = np.minimum(boxes[:, 0], boxes[:, 2]), np.maximum(boxes[:, 0], boxes[:, 2])
+    x1, x2 = np.minimum(boxes[:, 1], boxes[:, 3]), np.maximum(boxes[:, 1], boxes[:, 3])
+    area = (y2 - y1) * (x2 - x1)
+    thr = np.float32(iou_thr)
+    zero = np.float32(0)
+    kept: list[int] = []
+    for i in order.tolist():
+        if len(kept) >= max_out:
+            break
+        if kept and area[i] > 0:
+            k = np.asarray(kept)
+            inter = np.maximum(zero, np.minimum(y2[i], y2[k]) - np.maximum(y1[i], y1[k])) * \
+                np.maximum(zero, np.minimum(x2[i], x2[k]) - np.maximum(x1[i], x1[k]))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                iou = np.where(area[k] > 0, inter / ((area[i] + area[k]) - inter), zero)
+            if bool((iou > thr).any()):
+                continue
+        kept.append(i)
+    return kept
+
+
+def combined_nms_host(boxes, scores, max_per_class, max_total, iou_threshold, score_threshold, pad_per_class=False,
+                      clip_boxes=True):
+    """``CombinedNonMaxSuppression`` on host tensors: ``boxes`` [B, N, q, 4] (q = 1 or C),
+    ``scores`` [B, N, C].  Returns ``(boxes [B, T, 4], scores [B, T], classes [B, T])`` fp32 and
+    ``valid [B]`` int32; rows past ``valid`` are zero."""
+    import numpy as np
+
+    bx = torch.as_tensor(boxes).detach().float().cpu().numpy()
+    sc = torch.as_tensor(scores).detach().float().cpu().numpy()
+    if bx.ndim != 4 or sc.ndim != 3 or bx.shape[3] != 4 or bx.shape[:2] != sc.shape[:2]:
+        raise ValueError(f"combined_nms: boxes {bx.shape} / scores {sc.shape} are not [B,N,q,4] / [B,N,C]")
+    B, N, C = sc.shape
+    q = bx.shape[2]
+    if q not in (1, C):
+        raise ValueError(f"combined_nms: boxes have q={q} per-class boxes, expected 1 or {C}")
+    mpc, T = int(max_per_class), int(max_total)
+    if mpc < 1 or T < 1:
+        raise ValueError("combined_nms: max_output_size_per_class and max_total_size must be positive")
+    if pad_per_class:
+        T = min(T, mpc * C)
+    sc = sc + np.float32(0)  # -0.0 is 0.0: equal scores
+    ob = np.zeros((B, T, 4), np.float32)
+    os_ = np.zeros((B, T), np.float32)
+    oc = np.zeros((B, T), np.float32)
+    ov = np.zeros((B,), np.int32)
+    for b in range(B):
+        ent = []
+        for c in range(C):
+            cb = bx[b, :, c if q > 1 else 0]
+            for i in _nms_class_np(cb, sc[b, :, c], min(mpc, N), float(iou_threshold), np.float32(score_threshold)):
+                ent.append((-float(sc[b, i, c]), c, i))
+        ent.sort()
+        ent = ent[:T]
+        ov[b] = len(ent)
+        for t, (_, c, i) in enumerate(ent):
+            ob[b, t] = bx[b, i, c if q > 1 else 0]
+            os_[b, t] = sc[b, i, c]
+            oc[b, t] = c
+    if clip_boxes:
+        ob = np.clip(ob, np.float32(0), np.float32(1))
+    return torch.from_numpy(ob), torch.from_numpy(os_), torch.from_numpy(oc), torch.from_numpy(ov)
+
+
+def _scalar(t):
+    return torch.as_tensor(t).reshape(-1)[0].item()
+
+
+@register("CombinedNonMaxSuppression")
+def _combined_nms(ctx, node, boxes, scores, max_per_class, max_total, iou_thr, score_thr):
+    outs = combined_nms_host(boxes, scores, int(_scalar(max_per_class)), int(_scalar(max_total)),
+                             float(_scalar(iou_thr)), float(_scalar(score_thr)),
+                             bool(node.attr("pad_per_class", False)), bool(node.attr("clip_boxes", True)))
+    return tuple(o.to(boxes.device) for o in outs)
+
+
+def _nms_single(node, boxes, scores, max_out, iou_thr, score_thr, pad):
+    import numpy as np
+
+    bx = torch.as_tensor(boxes).detach().float().cpu().numpy()
+    sc = torch.as_tensor(scores).detach().float().cpu().numpy()
+    if bx.ndim != 2 or bx.shape[1] != 4 or sc.shape != (bx.shape[0],):
+        raise ValueError(f"{node.op}: boxes {bx.shape} / scores {sc.shape} are not [N,4] / [N]")
+    m = int(_scalar(max_out))
+    kept = _nms_class_np(bx, sc + np.float32(0), m, float(_scalar(iou_thr)), np.float32(score_thr))
+    valid = len(kept)
+    sel_scores = sc[kept] if kept else np.zeros((0,), np.float32)
+    if pad:
+        kept = kept + [0] * (m - valid)
+        sel_scores = np.concatenate([sel_scores, np.zeros((m - valid,), np.float32)])
+    dev = boxes.device
+    return (torch.tensor(kept, dtype=torch.int32, device=dev), torch.from_numpy(np.asarray(sel_scores, np.float32)).to(dev),
+            torch.tensor(valid, dtype=torch.int32, device=dev))
+
+
+@register("NonMaxSuppressionV2")
+def _nms_v2(ctx, node, boxes, scores, max_out, iou_thr):
+    return _nms_single(node, boxes, scores, max_out, iou_thr, float("-inf"), False)[:1]
+
+
+@register("NonMaxSuppressionV3")
+def _nms_v3(ctx, node, boxes, scores, max_out, iou_thr, score_thr):
+    return _nms_single(node, boxes, scores, max_out, iou_thr, _scalar(score_thr), False)[:1]
+
+
+@register("NonMaxSuppressionV4")
+def _nms_v4(ctx, node, boxes, scores, max_out, iou_thr, score_thr):
+    idx, _, valid = _nms_single(node, boxes, scores, max_out, iou_thr, _scalar(score_thr),
+                                bool(node.attr("pad_to_max_output_size", False)))
+    return idx, valid
+
+
+@register("NonMaxSuppressionV5")
+def _nms_v5(ctx, node, boxes, scores, max_out, iou_thr, score_thr, soft_nms_sigma):
+    if float(_scalar(soft_nms_sigma)) != 0.0:
+        raise NotImplementedError(f"{node.op} {node.name}: soft_nms_sigma != 0 (Soft-NMS) is not supported")
+    return _nms_single(node, boxes, scores, max_out, iou_thr, _scalar(score_thr),
+                       bool(node.attr("pad_to_max_output_size", False)))

@@ -49,6 +49,13 @@ class Val:
     pre_cfg: dict | None = None
     pre_chain: set | None = None
     pre_params: dict | None = None
+    # detection heads (``detection_lowering.py``): values without a step or a buffer that only
+    # a ``CombinedNonMaxSuppression`` reads.  ``decode_of`` = (encodings Val, anchors fp32
+    # [N, 4], four reciprocal scales): the boxes of a matched ``decode_boxes`` subgraph, decoded
+    # inside the ``nms`` step.  ``slice_of`` = (source Val, first column): a last-axis slice of
+    # the scores, read in place through a pitch and a class offset.
+    decode_of: tuple | None = None
+    slice_of: tuple | None = None
 
     @property
     def is_const(self):

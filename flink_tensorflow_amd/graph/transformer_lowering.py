@@ -413,7 +413,8 @@ class TransformerLowering:
     def _lower_group(self, grp) -> bool:
         """Lowers a matched group (False: its constants do not validate -> op by op)."""
         kind = grp["kind"]
-        ok = {"ln": self._lower_ln_group, "attn": self._lower_attn_group, "emb": self._lower_emb_group}[kind](grp)
+        ok = {"ln": self._lower_ln_group, "attn": self._lower_attn_group, "emb": self._lower_emb_group,
+              "decode": self._lower_decode_group}[kind](grp)  # "decode": detection_lowering.py
         if ok:
             grp["done"] = True
             for m in grp["members"]:

@@ -274,6 +274,58 @@ class DeepLabV3Model(ImageClassifierModel):
         return list(br.outputs[0][: br.n].numpy()), br.tags, br.latencies
 
 
+class SSDMobileNetModel(ImageClassifierModel):
+    """SSD-MobileNet-V1 (random-init frozen graph): object detection.  The plan is strict: the
+    MobileNet-V1 backbone on the depthwise kernel and the implicit GEMM, the box and class
+    predictors with zero-padded filters, and box decoding + the background-column slice +
+    ``CombinedNonMaxSuppression`` as one ``nms`` step (``kernels/detection.hip``), so a batch
+    returns ``max_total`` boxes per image instead of the raw heads.  Results are, per image, a
+    list of ``(score, label, (ymin, xmin, ymax, xmax))`` cut at ``num_detections``, best first,
+    from ``detect`` and from the batched ``submit`` / ``poll`` / ``drain`` path alike.  Class
+    indices are background-free: ``label_of(0)`` is the first real class."""
+
+    def __init__(self, image_hw=(300, 300), buckets=(8, 32), seed: int = 0, device=None, alpha: float = 1.0,
+                 num_classes: int = 90, max_per_class: int = 100, max_total: int = 100, iou_threshold: float = 0.6,
+                 score_threshold: float = 1e-8,
+                 fetches=("detection_boxes:0", "detection_scores:0", "detection_classes:0", "num_detections:0"), **kw):
+        self.seed = seed
+        self.alpha = alpha
+        self.num_classes = num_classes
+        self.nms = (max_per_class, max_total, iou_threshold, score_threshold)
+        from .ssd import ssd_batch_ok
+
+        bad = [b for b in buckets if not ssd_batch_ok(b, tuple(image_hw), num_classes)]
+        if bad:
+            raise ValueError(f"SSDMobileNetModel: buckets {bad} do not compile: batch * anchors * (num_classes + 1) must "
+                             "be a multiple of 8 (at 300 x 300 and 90 classes: a batch that is a multiple of 8)")
+        super().__init__(self._make_graph, image_hw, buckets, 1, device=device, fetches=fetches, **kw)
+
+    def _make_graph(self) -> GraphDef:
+        from .ssd import ssd_mobilenet_v1_graph_def
+
+        mpc, tot, iou, thr = self.nms
+        return ssd_mobilenet_v1_graph_def(num_classes=self.num_classes, image_hw=self.image_hw, alpha=self.alpha,
+                                          seed=self.seed, max_per_class=mpc, max_total=tot, iou_threshold=iou,
+                                          score_threshold=thr)
+
+    def _detections(self, boxes, scores, classes, valid) -> list[list[tuple]]:
+        out = []
+        for bx, sc, cl, n in zip(boxes.tolist(), scores.tolist(), classes.tolist(), valid.tolist()):
+            out.append([(sc[i], self.label_of(int(cl[i])), tuple(bx[i])) for i in range(int(n))])
+        return out
+
+    def detect(self, images) -> list[list[tuple]]:
+        """Per image the detections ``(score, label, (ymin, xmin, ymax, xmax))``, best first
+        (synchronous)."""
+        return self._detections(*self._run_sync(images))
+
+    def _sync_results(self, records):
+        return self.detect(records)
+
+    def _results(self, br):
+        return self._detections(*(o[: br.n] for o in br.outputs[:4])), br.tags, br.latencies
+
+
 class InceptionV3Model(ImageClassifierModel):
     """Inception-v3 (random-init frozen graph) compiled for fp8 by default — BASELINE config
     5: e4m3 weights and activations on the CDNA4 fp8 MFMA, bucketed dynamic batching per

@@ -963,6 +963,123 @@ def resize_argmax_nhwc(x: torch.Tensor, out_hw=None, align_corners: bool = False
     return out
 
 
+# ------------------------------------------------------------------------------ detection: box decode + NMS
+# The envelope of ``kernels/detection.hip``, from its LDS budget (160 KiB per CU).  The
+# per-class kernel sorts ``N`` rounded up to a power of two 8-byte keys (at most 4096 * 8 B =
+# 32 KiB) and keeps ``max_per_class`` canonical boxes with their areas (at most 256 * 20 B =
+# 5 KiB): dynamic LDS sized per launch, always under 64 KiB, so no function attribute has to be
+# set (18 KiB for an SSD's N = 1917 and 100 per class: eight workgroups per CU).  The merge
+# kernel gives every class one of its 256 threads and stages 16 keys per class (32 KiB) next
+# to the ``max_total`` merged keys (1024 * 8 B = 8 KiB), static.  Class and box index travel in
+# 16 bits each of a kept key.  Per-class boxes (q = C) have no kernel.
+NMS_MAX_BOXES = 4096
+NMS_MAX_CLASSES = 256
+NMS_MAX_PER_CLASS = 256
+NMS_MAX_TOTAL = 1024
+
+
+def nms_eligible(N: int, C: int, max_per_class: int, max_total: int, q: int = 1) -> bool:
+    """What ``combined_nms`` takes on the GPU (the lowering asks before it emits an ``nms`` step)."""
+    return (q == 1 and 1 <= N <= NMS_MAX_BOXES and 1 <= C <= NMS_MAX_CLASSES
+            and 1 <= max_per_class <= NMS_MAX_PER_CLASS and 1 <= max_total <= NMS_MAX_TOTAL)
+
+
+def nms_scratch_numel(B: int, C: int, max_per_class: int) -> int:
+    """int64 elements of the scratch ``combined_nms`` needs: the kept keys ``[B, C,
+    max_per_class]`` and, behind them, the int32 kept counts ``[B, C]``."""
+    return B * C * min(max_per_class, NMS_MAX_PER_CLASS) + (B * C + 1) // 2
+
+
+def combined_nms(boxes: torch.Tensor, scores: torch.Tensor, max_per_class: int, max_total: int, iou_threshold: float,
+                 score_threshold: float, pad_per_class: bool = False, clip_boxes: bool = True,
+                 anchors: torch.Tensor | None = None, box_scales=None, num_classes: int | None = None,
+                 class_offset: int = 0, out=None, scratch: torch.Tensor | None = None):
+    """TF ``CombinedNonMaxSuppression`` with one box per anchor shared by the classes
+    (``graph/ops_nn.py:combined_nms_host`` is the definition, ties pinned there).
+
+    ``scores`` is ``[B, N, ld]`` bf16 or fp32; the classes are its columns ``class_offset ..
+    class_offset + num_classes`` (all of them by default), read in place.  ``boxes`` is
+    ``[B, N, 1, 4]`` or ``[B, N, 4]`` bf16 or fp32 corners (ymin, xmin, ymax, xmax); with
+    ``anchors`` (fp32 ``[N, 4]`` = yc, xc, h, w) and ``box_scales`` (four reciprocal scale
+    factors) it holds bf16 or fp32 encodings (ty, tx, th, tw) instead, decoded in fp32 inside the kernel
+    (``ops_nn.decode_boxes_yxhw`` is the order of operations).  Returns ``(boxes [B, T, 4],
+    scores [B, T], classes [B, T])`` fp32 and ``valid [B]`` int32, ``T = max_total`` (with
+    ``pad_per_class``, ``min(max_total, max_per_class * C)``); rows past ``valid`` are zero.
+    ``out`` is that tuple preallocated and ``scratch`` an int64 tensor of ``nms_scratch_numel``
+    elements: a captured launch passes both, so nothing is allocated."""
+    if boxes.dim() == 4 and boxes.shape[2] == 1:
+        boxes = boxes[:, :, 0]
+    fused = anchors is not None
+    if boxes.dim() != 3 or boxes.shape[-1] != 4 or scores.dim() != 3 or tuple(boxes.shape[:2]) != tuple(scores.shape[:2]):
+        raise ValueError(f"combined_nms: boxes {tuple(boxes.shape)} / scores {tuple(scores.shape)} are not "
+                         "[B,N,(1,)4] / [B,N,C]")
+    B, N, ld = scores.shape
+    C = ld - class_offset if num_classes is None else int(num_classes)
+    if class_offset < 0 or C < 1 or class_offset + C > ld:
+        raise ValueError(f"combined_nms: classes {class_offset}..{class_offset + C} outside the {ld} score columns")
+    mpc, T = int(max_per_class), int(max_total)
+    if B < 1 or N < 1 or mpc < 1 or T < 1:
+        raise ValueError("combined_nms: empty problem")
+    if pad_per_class:
+        T = min(T, mpc * C)
+    mpc = min(mpc, N)  # selection stops at min(max_per_class, N)
+    if fused:
+        if box_scales is None or len(box_scales) != 4 or tuple(anchors.shape) != (N, 4):
+            raise ValueError(f"combined_nms: fused decode needs anchors [{N}, 4] and four box_scales")
+        box_scales = [float(v) for v in box_scales]
+    if not scores.is_cuda:
+        from ..graph.ops_nn import combined_nms_host, decode_boxes_yxhw
+
+        bx = decode_boxes_yxhw(boxes, anchors, box_scales) if fused else boxes.float()
+        res = combined_nms_host(bx[:, :, None], scores[..., class_offset:class_offset + C].float(), mpc, T,
+                                iou_threshold, score_threshold, False, clip_boxes)
+        if out is None:
+            return res
+        for o, r in zip(out, res):
+            o.copy_(r)
+        return tuple(out)
+    if not nms_eligible(N, C, mpc, T):
+        raise ValueError(f"combined_nms: N={N}, C={C}, max_per_class={mpc}, max_total={T} outside the kernel's "
+                         f"envelope ({NMS_MAX_BOXES}, {NMS_MAX_CLASSES}, {NMS_MAX_PER_CLASS}, {NMS_MAX_TOTAL})")
+    dev = scores.device
+    if scores.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"combined_nms: scores are bf16 or fp32, not {scores.dtype}")
+    _check(scores, "scores", scores.dtype, dev)
+    if fused:
+        if boxes.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"combined_nms: encodings are bf16 or fp32, not {boxes.dtype}")
+        _check(boxes, "boxes (encodings)", boxes.dtype, dev)
+        _check(anchors, "anchors", torch.float32, dev)
+        mode = 2 if boxes.dtype == torch.bfloat16 else 3
+    else:
+        if boxes.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"combined_nms: boxes are bf16 or fp32, not {boxes.dtype}")
+        _check(boxes, "boxes", boxes.dtype, dev)
+        mode = 0 if boxes.dtype == torch.float32 else 1
+        box_scales = [0.0] * 4
+    if out is None:
+        out = (torch.empty((B, T, 4), dtype=torch.float32, device=dev), torch.empty((B, T), dtype=torch.float32, device=dev),
+               torch.empty((B, T), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev))
+    ob, os_, oc, ov = out
+    for t, name, shape, dt in ((ob, "out boxes", (B, T, 4), torch.float32), (os_, "out scores", (B, T), torch.float32),
+                               (oc, "out classes", (B, T), torch.float32), (ov, "out valid", (B,), torch.int32)):
+        _check(t, name, dt, dev)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"combined_nms: {name} {tuple(t.shape)} is not {shape}")
+    need = nms_scratch_numel(B, C, mpc)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.int64, device=dev)
+    _check(scratch, "scratch", torch.int64, dev)
+    if scratch.numel() < need:
+        raise ValueError(f"combined_nms: scratch has {scratch.numel()} int64 elements, {need} needed")
+    _hip().combined_nms(boxes.data_ptr(), mode, _ptr(anchors), *box_scales, scores.data_ptr(),
+                        scores.dtype == torch.float32, B, N, C, ld, class_offset, mpc, T, float(iou_threshold),
+                        float(score_threshold), bool(clip_boxes), scratch.data_ptr(),
+                        scratch.data_ptr() + 8 * B * C * mpc, ob.data_ptr(), os_.data_ptr(), oc.data_ptr(), ov.data_ptr(),
+                        _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------ pooling
 def pool2d_nhwc(x: torch.Tensor, ksize, stride, pad=(0, 0, 0, 0), mode="max", out=None, out_channel_offset=0):
     N, H, W, C = x.shape
