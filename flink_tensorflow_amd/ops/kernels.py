@@ -1376,12 +1376,15 @@ def conv2d_direct(x: torch.Tensor, w_arr: torch.Tensor, kshape, Cout: int, bias:
     the per-channel dequant scale ``chan_scale``); ``w_arr`` from :func:`dconv_weights`;
     ``out_scale`` → e4m3 output.  ``maxpool_pad = (top, bottom, left, right)`` fuses a 3x3 /
     stride-2 max pool of the ReLU output (ResNet stem → pool1).  ``waves`` (4 or 8, default
-    default 8 for ``bn=64`` and 4 for ``bn=32``) sets the workgroup / tile size: 8 waves cover 32 x 16 conv
+    8 for ``bn=64`` and 4 for ``bn=32``) sets the workgroup / tile size: 8 waves cover 32 x 16 conv
     pixels (pooled: 14 x 8 pooled pixels, ``pool_rows=14``; 4 waves = 16 x 16 / 7 x 8) and
     fetch the filter bank half as often; tiles whose patch would not fit LDS fall back to 4.
+    The kernel has one stride for both axes: ``stride[0] != stride[1]`` is refused.
     Device-only (the host paths use the reference convs)."""
     N, H, W, Cin = x.shape
     KH, KW = kshape
+    if stride[0] != stride[1]:
+        raise ValueError(f"conv2d_direct: stride {tuple(stride)} must be the same on both axes")
     s = stride[0]
     pt, pb, pl, pr = pad
     Ho, Wo = conv_out_hw(H, W, KH, KW, s, s, pt, pl, 1, 1, pb, pr)
@@ -1403,6 +1406,10 @@ def conv2d_direct(x: torch.Tensor, w_arr: torch.Tensor, kshape, Cout: int, bias:
     _check(x, "x", x.dtype, x.device)
     _check(w_arr, "w", torch.uint8, x.device)
     _check(bias, "bias", torch.float32, x.device)
+    if chan_scale is not None:
+        _check(chan_scale, "chan_scale", torch.float32, x.device)
+    if bias.numel() < Cout or (chan_scale is not None and chan_scale.numel() < Cout):
+        raise ValueError(f"conv2d_direct: bias / chan_scale shorter than Cout = {Cout}")  # read as float4 per quad
     _check(out, "out", torch.uint8 if out_fp8 else torch.bfloat16, x.device)  # the kernel writes out_fp8 ? 1 : 2 B
     _hip().dconv(x.data_ptr(), w_arr.data_ptr(), _ptr(chan_scale), bias.data_ptr(), out.data_ptr(), es, N, H, W, Cin,
                  Cout, KH, KW, s, pt, pl, Ho, Wo, w_arr.shape[1], out.shape[3], out_channel_offset, int(out_fp8),
