@@ -232,6 +232,30 @@ class GraphBuilder:
                         scalar("score_threshold", score_threshold, np.float32)],
                        name=name, pad_per_class=bool(pad_per_class), clip_boxes=bool(clip_boxes))
 
+    def transpose(self, x, perm, name=None) -> str:
+        p = self.constant(f"{(name or 'transpose')}/perm", np.asarray(perm, dtype=np.int32))
+        return self.op("Transpose", [x, p], name=name or "transpose", Tperm=DataType.INT32)
+
+    def block_lstm(self, x, w, b, cs_prev, h_prev, seq_len_max, hidden, wci=None, wcf=None, wco=None,
+                   forget_bias=1.0, cell_clip=3.0, name=None) -> str:
+        """``BlockLSTM`` over time-major ``x [T, B, I]`` with ``w [I + H, 4H]`` / ``b [4H]`` (gate
+        columns i, ci, f, o).  Returns the node NAME: the outputs are ``name:0 .. name:6`` =
+        i, cs, f, o, ci, co, h.  ``seq_len_max`` is a number or a tensor name; the peephole is on
+        when the three vectors are given (else zero vectors of ``hidden`` elements are wired in, as
+        TF does)."""
+        nm = name or "BlockLSTM"
+        peep = wci is not None
+        if peep != (wcf is not None) or peep != (wco is not None):
+            raise ValueError("block_lstm: the three peephole vectors come together")
+        if not isinstance(seq_len_max, str):
+            seq_len_max = self.constant(f"{nm}/seq_len_max", np.asarray(seq_len_max, dtype=np.int64))
+        if not peep:
+            zero = self.constant(f"{nm}/no_peephole", np.zeros((hidden,), dtype=np.float32))
+            wci = wcf = wco = zero
+        out = self.op("BlockLSTM", [seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b], name=name,
+                      forget_bias=float(forget_bias), cell_clip=float(cell_clip), use_peephole=peep, T=DataType.FLOAT)
+        return out.split(":")[0]
+
     def top_k(self, x, k, name=None) -> str:
         kk = self.constant(f"{(name or 'TopKV2')}/k", np.asarray(k, dtype=np.int32))
         return self.op("TopKV2", [x, kk], name=name, sorted=True)

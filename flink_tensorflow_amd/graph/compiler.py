@@ -21,6 +21,9 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``[decode_boxes subgraph] + [last-axis score slice] → CombinedNonMaxSuppression`` → one
      ``nms`` step: box decoding, per-class greedy NMS and the top-T merge
      (kernels/detection.hip, ``detection_lowering.py``);
+   * ``[Transpose] → BlockLSTM → [Transpose | last-step StridedSlice]`` → one projection
+     ``gemm`` step plus one ``lstm`` step that walks the whole sequence (kernels/lstm.hip,
+     ``recurrent_lowering.py``); the layout ops emit nothing;
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -34,12 +37,13 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is five modules: ``plan.py`` (``Val``, ``Step``, ``CompileError`` and the
+The compiler is six modules: ``plan.py`` (``Val``, ``Step``, ``CompileError`` and the
 helpers that map a value to its buffer; re-exported here), ``conv_lowering.py`` (the
 ``ConvLowering`` mixin: Conv2D chains, the pure kernel choice ``select_conv_kernel`` and the
 block-tail post-passes), ``transformer_lowering.py`` (the ``TransformerLowering`` mixin: BERT
 patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering`` mixin: box
-decoding + NMS) and this one (pruning, folding, MatMul / pooling / concat / glue
+decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering`` mixin: ``BlockLSTM`` and the
+layout ops around it) and this one (pruning, folding, MatMul / pooling / concat / glue
 lowering, memory planning, the batch-slice chain, capture and replay).
 
 Activations are bf16 NHWC on device; fetched outputs are cast back to the graph dtype.
@@ -75,6 +79,7 @@ from .graph import Graph, Node
 from .op_registry import OpContext, lookup
 from .ops_nn import same_pads
 from .plan import CompileError, Step, Val, _buf_shape, _cfg, _coff, _eff_scale, _host, _nbytes, _root, _target, _view
+from .recurrent_lowering import RecurrentLowering
 from .transformer_lowering import TransformerLowering
 
 __all__ = ["CompiledFunction", "CompileError", "Step", "Val", "compile_signature"]
@@ -97,7 +102,7 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, DetectionLowering, ConvLowering):
+class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, ConvLowering):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -428,6 +433,10 @@ class CompiledFunction(TransformerLowering, DetectionLowering, ConvLowering):
             return self._lower_combined_nms(node)
         if op in _UNPADDED_NMS:
             return self._lower_unpadded_nms(node)
+        if op == "BlockLSTM":
+            return self._lower_block_lstm(node)
+        if op == "Transpose" and self._lower_tb_transpose(node):
+            return
         if op in ("MaxPool", "AvgPool"):
             return self._lower_pool(node)
         if op == "Mean":

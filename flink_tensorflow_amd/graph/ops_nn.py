@@ -384,3 +384,44 @@ def _nms_v5(ctx, node, boxes, scores, max_out, iou_thr, score_thr, soft_nms_sigm
         raise NotImplementedError(f"{node.op} {node.name}: soft_nms_sigma != 0 (Soft-NMS) is not supported")
     return _nms_single(node, boxes, scores, max_out, iou_thr, _scalar(score_thr),
                        bool(node.attr("pad_to_max_output_size", False)))
+
+
+def block_lstm(seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b, forget_bias=1.0, cell_clip=3.0,
+               use_peephole=False):
+    """TF ``BlockLSTM`` (the fused cell of ``LSTMBlockFusedCell``): ``x [T, B, I]``, ``w [I + H,
+    4H]`` and ``b [4H]`` with gate columns in the order i, ci, f, o.  Returns ``(i, cs, f, o, ci,
+    co, h)``, each ``[T, B, H]``; steps ``t >= seq_len_max`` of every output are zero."""
+    if x.dim() != 3 or cs_prev.dim() != 2 or w.dim() != 2:
+        raise ValueError(f"BlockLSTM: x {tuple(x.shape)} / cs_prev {tuple(cs_prev.shape)} / w {tuple(w.shape)} are not "
+                         "[T,B,I] / [B,H] / [I+H,4H]")
+    T, B, I = x.shape
+    H = cs_prev.shape[1]
+    if tuple(w.shape) != (I + H, 4 * H) or tuple(h_prev.shape) != (B, H) or tuple(cs_prev.shape) != (B, H) \
+            or b.numel() != 4 * H:
+        raise ValueError(f"BlockLSTM: w {tuple(w.shape)}, b {tuple(b.shape)}, h_prev {tuple(h_prev.shape)} do not match "
+                         f"T={T}, B={B}, I={I}, H={H}")
+    steps = max(0, min(T, int(_scalar(seq_len_max))))
+    outs = [torch.zeros((T, B, H), dtype=x.dtype, device=x.device) for _ in range(7)]
+    cs, h = cs_prev, h_prev
+    for t in range(steps):
+        gi, gc, gf, go = (torch.cat([x[t], h], dim=1) @ w + b).split(H, dim=1)
+        gf = gf + forget_bias
+        if use_peephole:
+            gi, gf = gi + cs * wci, gf + cs * wcf
+        gi, gf, ci = torch.sigmoid(gi), torch.sigmoid(gf), torch.tanh(gc)
+        cs = ci * gi + cs * gf
+        if cell_clip > 0:
+            cs = cs.clamp(-cell_clip, cell_clip)
+        if use_peephole:
+            go = go + cs * wco
+        go, co = torch.sigmoid(go), torch.tanh(cs)
+        h = co * go
+        for o, v in zip(outs, (gi, cs, gf, go, ci, co, h)):
+            o[t] = v
+    return tuple(outs)
+
+
+@register("BlockLSTM")
+def _block_lstm(ctx, node, seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b):
+    return block_lstm(seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b, float(node.attr("forget_bias", 1.0)),
+                      float(node.attr("cell_clip", 3.0)), bool(node.attr("use_peephole", False)))

@@ -56,6 +56,10 @@ class Val:
     # the scores, read in place through a pitch and a class offset.
     decode_of: tuple | None = None
     slice_of: tuple | None = None
+    # recurrent layers (``recurrent_lowering.py``): the time-major ``[T, B, I]`` result of an
+    # absorbed ``Transpose`` that only a ``BlockLSTM`` reads, without a step or a buffer;
+    # ``tm_of`` is the batch-major ``[B, T, I]`` source Val, read in place through strides
+    tm_of: "Val | None" = None
 
     @property
     def is_const(self):

@@ -1,7 +1,8 @@
 """Model zoo.  The model classes load lazily: importing the package pulls in no compiler."""
 _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "mobilenet",
             "DeepLabV3Model": "image_classifier", "deeplab_v3_graph_def": "deeplab",
-            "SSDMobileNetModel": "image_classifier", "ssd_mobilenet_v1_graph_def": "ssd"}
+            "SSDMobileNetModel": "image_classifier", "ssd_mobilenet_v1_graph_def": "ssd",
+            "LSTMClassifierModel": "lstm", "lstm_classifier_graph_def": "lstm"}
 
 __all__ = sorted(_EXPORTS)
 

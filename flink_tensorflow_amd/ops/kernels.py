@@ -1080,6 +1080,153 @@ def combined_nms(boxes: torch.Tensor, scores: torch.Tensor, max_per_class: int, 
     return out
 
 
+# ------------------------------------------------------------------------------ LSTM recurrence
+LSTM_MAX_HIDDEN = 512
+LSTM_RESIDENT_HIDDEN = 128  # up to here the recurrent weights stay in registers for all steps
+
+
+def lstm_eligible(T: int, B: int, I: int, H: int) -> bool:
+    """What ``lstm_seq`` (and the projection GEMM in front of it) takes on the GPU."""
+    return T >= 1 and B >= 1 and I >= 8 and I % 8 == 0 and 16 <= H <= LSTM_MAX_HIDDEN and H % 16 == 0
+
+
+def lstm_impl(H: int) -> str:
+    """The form of ``kernels/lstm.hip`` the launcher picks for ``H`` hidden units."""
+    return "lstm_resident" if H <= LSTM_RESIDENT_HIDDEN else "lstm_streamed"
+
+
+def lstm_pack_weights(wh: torch.Tensor, H: int) -> torch.Tensor:
+    """The recurrent weights ``wh [H, 4H]`` (gate columns i, ci, f, o: ``w[I:]`` of a
+    ``BlockLSTM``) as the A fragments of ``v_mfma_f32_16x16x32_bf16`` with gate units on M:
+    ``[H/16, 4, KS, 64, 8]`` bf16, ``KS = ceil(H / 32)``, where element ``e`` of lane ``l`` in
+    ``[u, g, ks]`` is ``wh[32 ks + 8 (l >> 4) + e, g H + 16 u + (l & 15)]`` and rows past ``H``
+    (the upper half of the last K step when ``H % 32 == 16``) are zero."""
+    if wh.dim() != 2 or tuple(wh.shape) != (H, 4 * H) or H % 16 or H < 16:
+        raise ValueError(f"lstm_pack_weights: weights {tuple(wh.shape)} are not [H, 4H] with H = {H} a multiple of 16")
+    KS = -(-H // 32)
+    w = torch.zeros((KS * 32, 4 * H), dtype=torch.bfloat16, device=wh.device)
+    w[:H] = wh.to(torch.bfloat16)
+    w = w.reshape(KS, 4, 8, 4, H // 16, 16)  # [ks, lane >> 4, e, gate, unit group, lane & 15]
+    return w.permute(4, 3, 0, 1, 5, 2).reshape(H // 16, 4, KS, 64, 8).contiguous()
+
+
+def lstm_unpack_weights(wpk: torch.Tensor) -> torch.Tensor:
+    """Inverse of ``lstm_pack_weights``: ``[H, 4H]`` bf16."""
+    if wpk.dim() != 5 or tuple(wpk.shape[3:]) != (64, 8) or wpk.shape[1] != 4:
+        raise ValueError(f"lstm_unpack_weights: {tuple(wpk.shape)} is not [H/16, 4, KS, 64, 8]")
+    G, _, KS = wpk.shape[:3]
+    H = G * 16
+    if KS != -(-H // 32):
+        raise ValueError(f"lstm_unpack_weights: {KS} K steps do not belong to H = {H}")
+    w = wpk.reshape(G, 4, KS, 4, 16, 8).permute(2, 3, 5, 1, 0, 4).reshape(KS * 32, 4 * H)
+    return w[:H].contiguous()
+
+
+def lstm_seq(xproj: torch.Tensor, wh_packed: torch.Tensor, h0: torch.Tensor, c0: torch.Tensor, *,
+             wci: torch.Tensor | None = None, wcf: torch.Tensor | None = None, wco: torch.Tensor | None = None,
+             cell_clip: float = 3.0, steps: int | None = None, h_out: torch.Tensor | None = None,
+             cs_out: torch.Tensor | None = None, c_last: torch.Tensor | None = None,
+             last_only: bool = False) -> torch.Tensor:
+    """The recurrence of one ``BlockLSTM`` layer in one launch (``kernels/lstm.hip``).
+
+    ``xproj [T, B, 4H]`` bf16 is the input projection ``x . w[:I] + b`` (forget bias folded
+    in), gate columns i, ci, f, o; ``wh_packed = lstm_pack_weights(w[I:], H)``; ``h0 [B, H]``
+    bf16, ``c0 [B, H]`` fp32 or bf16; the peephole vectors fp32 ``[H]``, all three or none.
+    ``xproj``, ``h_out`` and ``cs_out`` are addressed through their own strides for ``t`` and
+    ``b`` (last axis contiguous): a batch-major buffer goes in as ``buf.transpose(0, 1)``.
+    ``h_out`` is ``[T, B, H]`` bf16, or ``[B, H]`` = the hidden state after the last step with
+    ``last_only``; ``cs_out [T, B, H]`` bf16 and ``c_last [B, H]`` fp32 (the cell state after
+    ``steps``) are optional.  Steps ``>= steps`` (default ``T``) of the ``[T, ..]`` outputs are
+    zero; ``steps == 0`` with ``last_only`` writes zeros.  ``cell_clip <= 0``: no clip.
+
+    Rounding points, the same on both paths: ``xproj`` is bf16; ``h`` is rounded to bf16
+    before it is stored and fed back; ``c`` is never rounded (``cs_out`` on store only)."""
+    if xproj.dim() != 3 or xproj.shape[-1] % 4:
+        raise ValueError(f"lstm_seq: xproj {tuple(xproj.shape)} is not [T, B, 4H]")
+    T, B, H4 = xproj.shape
+    H = H4 // 4
+    if T < 1 or B < 1 or H < 16 or H > LSTM_MAX_HIDDEN or H % 16:
+        raise ValueError(f"lstm_seq: T={T}, B={B}, H={H} outside the kernel's envelope (H a multiple of 16 in "
+                         f"16..{LSTM_MAX_HIDDEN})")
+    KS = -(-H // 32)
+    if tuple(wh_packed.shape) != (H // 16, 4, KS, 64, 8):
+        raise ValueError(f"lstm_seq: packed weights {tuple(wh_packed.shape)} are not {(H // 16, 4, KS, 64, 8)} "
+                         "(lstm_pack_weights)")
+    steps = T if steps is None else int(steps)
+    if not 0 <= steps <= T:
+        raise ValueError(f"lstm_seq: steps={steps} outside 0..{T}")
+    dev = xproj.device
+    peep = [wci, wcf, wco]
+    if any(p is None for p in peep) != all(p is None for p in peep):
+        raise ValueError("lstm_seq: the three peephole vectors come together")
+    peep = None if wci is None else peep
+    if xproj.dtype != torch.bfloat16 or xproj.stride(2) != 1:
+        raise TypeError("lstm_seq: xproj must be bf16 with a contiguous last axis")
+    _check(wh_packed, "wh_packed", device=dev)
+    _check(h0, "h0", device=dev)
+    if c0.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"lstm_seq: c0 is fp32 or bf16, not {c0.dtype}")
+    _check(c0, "c0", c0.dtype, dev)
+    if tuple(h0.shape) != (B, H) or tuple(c0.shape) != (B, H):
+        raise ValueError(f"lstm_seq: h0 {tuple(h0.shape)} / c0 {tuple(c0.shape)} are not [{B}, {H}]")
+    for p in peep or ():
+        _check(p, "peephole vector", torch.float32, dev)
+        if tuple(p.shape) != (H,):
+            raise ValueError(f"lstm_seq: peephole vector {tuple(p.shape)} is not [{H}]")
+    hshape = (B, H) if last_only else (T, B, H)
+    if h_out is None:
+        h_out = torch.empty(hshape, dtype=torch.bfloat16, device=dev)
+    for t, name, shape, dt in ((h_out, "h_out", hshape, torch.bfloat16), (cs_out, "cs_out", (T, B, H), torch.bfloat16),
+                               (c_last, "c_last", (B, H), torch.float32)):
+        if t is None:
+            continue
+        if t.dtype != dt or t.device != dev or tuple(t.shape) != shape or t.stride(-1) != 1:
+            raise ValueError(f"lstm_seq: {name} must be {dt} {shape} on {dev} with a contiguous last axis, got "
+                             f"{t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    if c_last is not None and not c_last.is_contiguous():
+        raise ValueError("lstm_seq: c_last must be contiguous")
+    clip = float(cell_clip)
+    if xproj.is_cuda:
+        views = [("xproj", xproj), ("h_out", h_out)] + ([("cs_out", cs_out)] if cs_out is not None else [])
+        for name, t in views:
+            if t.data_ptr() % 16 or any(s % 8 for s in t.stride()[:-1]):
+                raise ValueError(f"lstm_seq: {name} must be 16-byte aligned with row strides that are multiples of 8")
+            if min(t.stride()[:-1]) < t.shape[-1]:
+                raise ValueError(f"lstm_seq: {name} rows overlap (strides {t.stride()})")
+        hs_t, hs_b = (0, h_out.stride(0)) if last_only else (h_out.stride(0), h_out.stride(1))
+        cs_t, cs_b = (cs_out.stride(0), cs_out.stride(1)) if cs_out is not None else (0, 0)
+        _hip().lstm_seq_bf16(xproj.data_ptr(), wh_packed.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                             c0.dtype == torch.bfloat16, _ptr(wci), _ptr(wcf), _ptr(wco), h_out.data_ptr(), _ptr(cs_out),
+                             _ptr(c_last), T, B, H, steps, xproj.stride(0), xproj.stride(1), hs_t, hs_b, cs_t, cs_b,
+                             bool(last_only), clip, _stream())
+        return h_out
+    wh = lstm_unpack_weights(wh_packed).float()
+    c, h = c0.float(), h0.float()
+    if not last_only:
+        h_out[steps:] = 0
+    if cs_out is not None:
+        cs_out[steps:] = 0
+    for t in range(steps):
+        gi, gc, gf, go = (xproj[t].float() + h @ wh).split(H, dim=1)
+        if peep:
+            gi, gf = gi + c * wci, gf + c * wcf
+        c = torch.tanh(gc) * torch.sigmoid(gi) + c * torch.sigmoid(gf)
+        if clip > 0:
+            c = c.clamp(-clip, clip)
+        if peep:
+            go = go + c * wco
+        h = (torch.tanh(c) * torch.sigmoid(go)).to(torch.bfloat16).float()
+        if not last_only:
+            h_out[t] = h.to(torch.bfloat16)
+        if cs_out is not None:
+            cs_out[t] = c.to(torch.bfloat16)
+    if last_only:
+        h_out.copy_(h.to(torch.bfloat16) if steps else torch.zeros_like(h_out))
+    if c_last is not None:
+        c_last.copy_(c)
+    return h_out
+
+
 # ------------------------------------------------------------------------------ pooling
 def pool2d_nhwc(x: torch.Tensor, ksize, stride, pad=(0, 0, 0, 0), mode="max", out=None, out_channel_offset=0):
     N, H, W, C = x.shape
