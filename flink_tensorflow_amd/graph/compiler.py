@@ -37,14 +37,14 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is six modules: ``plan.py`` (``Val``, ``Step``, ``CompileError`` and the
-helpers that map a value to its buffer; re-exported here), ``conv_lowering.py`` (the
-``ConvLowering`` mixin: Conv2D chains, the pure kernel choice ``select_conv_kernel`` and the
-block-tail post-passes), ``transformer_lowering.py`` (the ``TransformerLowering`` mixin: BERT
-patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering`` mixin: box
-decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering`` mixin: ``BlockLSTM`` and the
-layout ops around it) and this one (pruning, folding, MatMul / pooling / concat / glue
-lowering, memory planning, the batch-slice chain, capture and replay).
+The compiler is eight modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
+pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
+``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
+mixin: box decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering`` mixin: ``BlockLSTM`` and the layout
+ops around it), ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
+``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
+bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
 
 Activations are bf16 NHWC on device; fetched outputs are cast back to the graph dtype.
 
@@ -59,8 +59,8 @@ pools requantise on the fly; anything else reads a dequantised bf16 copy.
 from __future__ import annotations
 
 import collections
+import contextlib
 import logging
-import types
 from typing import Any
 
 import numpy as np
@@ -70,7 +70,6 @@ from ..ops import fp8 as F8
 from ..ops import kernels as K
 from ..types.dtypes import DataType
 from ..types.names import TensorName
-from ..types.tensor import StringTensor
 from ..utils import tracing
 from . import ops_core  # noqa: F401
 from .conv_lowering import _ACTS, ConvLowering
@@ -78,7 +77,9 @@ from .detection_lowering import _UNPADDED_NMS, DetectionLowering
 from .graph import Graph, Node
 from .op_registry import OpContext, lookup
 from .ops_nn import same_pads
-from .plan import CompileError, Step, Val, _buf_shape, _cfg, _coff, _eff_scale, _host, _nbytes, _root, _target, _view
+from .plan import Chain, CompileError, Step, Val, _coff, _eff_scale, _host, _target, _view
+from .plan_memory import PlanMemory
+from .plan_run import PlanRunner
 from .recurrent_lowering import RecurrentLowering
 from .transformer_lowering import TransformerLowering
 
@@ -102,7 +103,7 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, ConvLowering):
+class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, ConvLowering, PlanMemory, PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -134,6 +135,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self.feed_names = [str(TensorName.parse(f)) for f in feeds]
         self.feed_specs = {str(TensorName.parse(f)): v for f, v in feeds.items()}
         self.fetch_names = [str(TensorName.parse(f)) for f in fetches]
+        self._fetched_nodes = frozenset(TensorName.parse(f).name for f in fetches)
         self.variables = variables or {}
         self.strict = strict
         self.steps: list[Step] = []
@@ -145,8 +147,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self._input_bufs: dict[str, torch.Tensor] = {}
         self._outputs: list = []
         self._graph_obj: torch.cuda.CUDAGraph | None = None
-        # graph of steps[1:] when steps[0] is the preprocess kernel reading a feed nothing else
-        # reads: ``replay_from`` then runs that kernel on the caller's staging buffer
+        # graph of steps[1:] and the (feed, step) of steps[0] when that is a head (``_head_feed_step``)
         self._graph_tail: torch.cuda.CUDAGraph | None = None
         self._head: tuple[str, Step] | None = None
         self._amax: dict[str, float] = {}
@@ -154,13 +155,9 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self.stats = collections.Counter(dict.fromkeys(_STATS, 0))
         self._debug_sync = tracing.debug_sync()
         self._poison_after: dict[int, list] = {}
-        # batch-slice chain (``_find_chain``): (first step, end step, slices, slice size,
-        # values whose full buffers are sliced per slice) or None
-        self._chain: tuple | None = None
+        self._chain: Chain | None = None  # the batch-slice chain (``PlanMemory._find_chain``)
         if self._debug_sync or tracing.debug_poison():
             use_graph = False  # debug modes act between launches: run the plan eagerly
-        import contextlib
-
         if precision == "fp8":  # calibrate activation ranges on a bf16 twin of the plan
             twin = CompiledFunction(graph, feeds, fetches, device, variables, use_graph=False, strict=strict)
             self._amax = twin.calibrate(calibration)
@@ -250,44 +247,6 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self._decimate_tails()
         self._chain_tails()
 
-    # ------------------------------------------------------------------ calibration
-    def synthetic_feeds(self, seed: int = 0) -> dict:
-        g = torch.Generator().manual_seed(seed)
-        out = {}
-        for f in self.feed_names:
-            shape, dt = self.feed_specs[f]
-            dt = DataType.of(dt).torch
-            if dt == torch.uint8:
-                out[f] = torch.randint(0, 256, tuple(shape), generator=g, dtype=torch.uint8)
-            elif dt.is_floating_point:
-                out[f] = torch.randn(tuple(shape), generator=g).to(dt)
-            else:
-                out[f] = torch.randint(0, 100, tuple(shape), generator=g).to(dt)
-        return out
-
-    @torch.no_grad()
-    def calibrate(self, feeds: dict | None = None) -> dict[str, float]:
-        """Runs the plan step by step on ``feeds`` (synthetic when None) and returns the
-        absolute maximum of every computed value, keyed by graph node name."""
-        for k, v in (feeds or self.synthetic_feeds()).items():
-            self.input_buffer(k).copy_(v)
-        by_id: dict[int, float] = {}
-
-        def each(s):  # a batch-slice chain step runs once per slice: max over the slices
-            s.fn()
-            for o in s.outputs:
-                t = _view(o)
-                if t.is_floating_point() and t.numel():
-                    k = id(_root(o))
-                    by_id[k] = max(by_id.get(k, 0.0), float(t.float().abs().max()))
-
-        self._run_range(0, len(self.steps), each)
-        for v in self.vals.values():  # concat targets: max over their stride-written children
-            kids = getattr(v, "_concat_children", None)
-            if kids:
-                by_id[id(v)] = max(by_id.get(id(_root(c)), 0.0) for c in kids)
-        return {n: by_id[id(_root(v))] for (n, _), v in self.vals.items() if id(_root(v)) in by_id}
-
     def _qscale(self, name: str) -> float | None:
         a = self._amax.get(name)
         return None if a is None else F8.scale_for(a)
@@ -295,13 +254,29 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
     def _fp8_consumers_ok(self, name: str) -> bool:
         """True when ``name``'s value may be stored as fp8: not fetched, and every consumer
         reads fp8 natively."""
-        if any(TensorName.parse(f).name == name for f in self.fetch_names):
+        if self._fetched(name):
             return False
         cons = self.cons.get(name, [])
         return bool(cons) and all(self.graph[c].op in ("Conv2D", "MaxPool", "AvgPool", "ConcatV2", "Mean")
                                   for c in cons)
 
     # ------------------------------------------------------------------ helpers
+    def _fetched(self, name: str) -> bool:
+        """Some output of graph node ``name`` is fetched."""
+        return name in self._fetched_nodes
+
+    def _readers(self, v: Val) -> set | None:
+        """The consumers of the graph nodes whose value is ``v``; None when one of those nodes is fetched."""
+        names = [n for (n, _), u in self.vals.items() if u is v]
+        if any(self._fetched(n) for n in names):
+            return None
+        return {c for n in names for c in self.cons.get(n, [])}
+
+    def _val_of(self, tensor_name: str) -> Val:
+        """The value of a feed or fetch, by its tensor name (``node:index``)."""
+        tn = TensorName.parse(tensor_name)
+        return self.vals[(tn.name, tn.index)]
+
     def _in(self, node: Node, i: int) -> Val:
         s, k = node.inputs[i]
         v = self._get((s, k))
@@ -317,8 +292,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
 
     def _single_consumer(self, name: str) -> Node | None:
         c = self.cons.get(name, [])
-        fetched = any(TensorName.parse(f).name == name for f in self.fetch_names)
-        if len(c) != 1 or fetched:
+        if len(c) != 1 or self._fetched(name):
             return None
         return self.graph[c[0]]
 
@@ -392,8 +366,8 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
     def _new(self, shape, dtype=torch.bfloat16, phys_c=None) -> Val:
         return Val(tuple(int(s) for s in shape), dtype, phys_c=phys_c)
 
-    def _emit(self, name, kind, fn, inputs, outputs, meta=None):
-        self.steps.append(Step(name, kind, fn, list(inputs), list(outputs), dict(meta or {})))
+    def _emit(self, name, kind, fn, inputs, outputs, meta=None, head=None):
+        self.steps.append(Step(name, kind, fn, list(inputs), list(outputs), dict(meta or {}), head))
 
     # ------------------------------------------------------------------ lowering
     def _lower(self, node: Node):
@@ -672,8 +646,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         if size is None:
             size = (x.shape[1], x.shape[2])
         out = self._new((x.shape[0], size[0], size[1], 3), phys_c=8)
-        out_buf_shape = (x.shape[0], size[0], size[1], 8)
-        out.buf_shape = out_buf_shape
+        out.buf_shape = (x.shape[0], size[0], size[1], 8)
         out.pre_cfg = {"s2d": False}
         out.pre_chain = {n.name for n in chain}
         # what a stem conv needs to absorb this kernel (dconv_u8s2d): no resize, the affine only
@@ -682,12 +655,11 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         for n in chain[1:]:
             self._fused.add(n.name)
         mean_t, std_t = tuple(mean.tolist()), tuple(std.tolist())
-        cfg = out.pre_cfg
 
-        def run(x=x, out=out):
-            K.preprocess_images(x.buf, size, mean_t, std_t, align, half, out=out.buf, s2d=cfg["s2d"])
+        def head(src, dst):  # ``s2d`` is read per launch: the stem conv flips it after this step is emitted
+            K.preprocess_images(src, size, mean_t, std_t, align, half, out=dst, s2d=out.pre_cfg["s2d"])
 
-        self._emit(cast.name + "/preprocess", "preprocess", run, [x], [out])
+        self._emit(cast.name + "/preprocess", "preprocess", lambda: head(x.buf, out.buf), [x], [out], head=head)
         for n in chain:
             self.vals[(n.name, 0)] = out
         return True
@@ -757,7 +729,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         x = self._in(node, 0)
         if x.is_const or not self._argmax_ok(node, tuple(x.shape)):
             return self._lower_glue(node)
-        src, align, half = getattr(x, "resize_of", (x, False, False))
+        src, align, half = x.resize_of or (x, False, False)
         if not self._resize_source_ok(src, pitch8=True):
             return self._lower_glue(node)
         N, Ho, Wo, C = x.shape
@@ -929,7 +901,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
                 v.concat_slot = (out, off)
                 off += v.shape[-1]
             self.vals[(node.name, 0)] = out
-            out._concat_children = ins
+            out.concat_children = ins
             return
         if fp8 or any(v.qscale is not None for v in ins):  # mixed scales: concatenate in bf16
             out = self._new(tuple(shape))
@@ -952,11 +924,9 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         if v.alias_of is not None or v.phys_c:
             return False
         # every graph node that maps to this value must feed only the concat
-        for (n, _), val in self.vals.items():
-            if val is v and any(c != concat_node and c not in self._fused for c in self.cons.get(n, [])):
-                return False
-            if val is v and any(TensorName.parse(f).name == n for f in self.fetch_names):
-                return False
+        readers = self._readers(v)
+        if readers is None or any(c != concat_node and c not in self._fused for c in readers):
+            return False
         if v.qscale is not None:
             return v.shape[-1] % 16 == 0 and src_node in self.cons
         return v.shape[-1] % 8 == 0 and v.dtype == torch.bfloat16 and src_node in self.cons
@@ -997,462 +967,6 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self._emit(node.name, "glue", run, [v for v in ins if not v.is_const], outv)
         for k, o in enumerate(outv):
             self.vals[(node.name, k)] = o
-
-    # ================================================================== memory
-    def _plan_memory_and_bind(self):
-        """Feeds and fetched values get persistent buffers (arena blocks); every other
-        produced value lives at a planned offset of one activation slab — lifetimes
-        [producing step, last reading step] never overlap in memory (native liveness
-        planner, ``batching/arena.py``).  With a subtask arena the slab is shared by all
-        of the subtask's plans (they replay serially on one stream)."""
-        from ..batching.arena import plan_offsets
-
-        for f in self.feed_names:
-            tn = TensorName.parse(f)
-            v = self.vals[(tn.name, tn.index)]
-            v.buf = self._persistent(v.shape, v.dtype)
-            self._input_bufs[f] = v.buf
-        fetch_vals = [self.vals[(TensorName.parse(f).name, TensorName.parse(f).index)] for f in self.fetch_names]
-        for i, s in enumerate(self.steps):
-            for v in s.inputs:
-                _root(v).last_use = max(_root(v).last_use, i)
-        keep = {id(_root(v)) for v in fetch_vals}
-        chain = self._find_chain(keep)
-        internal = chain["internal"] if chain else {}
-        owners: dict[int, Val] = {}   # buffer-owning values in order of first production
-        born: dict[int, int] = {}
-        for i, s in enumerate(self.steps):
-            for o in s.outputs:
-                r = _root(o)
-                if r.buf is not None:
-                    continue
-                tgt = r.concat_slot[0] if r.concat_slot else r  # branches write into their concat
-                if tgt.buf is None and id(tgt) not in owners:
-                    owners[id(tgt)] = tgt
-                    born[id(tgt)] = i
-        for t in owners.values():
-            t.last_use = max([t.last_use] + [c.last_use for c in getattr(t, "_concat_children", [])])
-        transient = []
-        for k, t in owners.items():
-            if k in internal:
-                continue  # slice-sized buffer in the chain's own slab (below)
-            if k in keep:
-                t.buf = self._persistent(_buf_shape(t), t.dtype)
-            else:
-                transient.append(t)
-        sizes = [_nbytes(_buf_shape(t), t.dtype) for t in transient]
-        first = [born[id(t)] for t in transient]
-        last = [max(born[id(t)], t.last_use) for t in transient]
-        if chain:
-            # a tensor the chain writes is written by its first slice pass and one it reads is
-            # read by its last: both live across the whole chain
-            i0, i1 = chain["range"]
-            for j, t in enumerate(transient):
-                if id(t) in chain["touched"]:
-                    if i0 <= first[j] < i1:
-                        first[j] = i0
-                    if last[j] >= i0:
-                        last[j] = max(last[j], i1 - 1)
-            # the slice-sized internals form one region of the same slab, live across the chain
-            chain_layout = self._plan_chain(chain, born)
-            sizes.append(max(chain_layout[1], 1))
-            first.append(i0)
-            last.append(i1 - 1)
-        offs, total = plan_offsets(sizes, first, last)
-        self.activation_bytes = total
-        slab = self.arena.shared_slab(total) if self.arena is not None else \
-            torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
-        for t, off, nb, lu in zip(transient, offs, sizes, last):
-            t.buf = slab[off:off + nb].view(t.dtype).view(tuple(_buf_shape(t)))
-            self._poison_after.setdefault(lu, []).append(t.buf)
-        if chain:
-            self._bind_chain(chain, chain_layout, slab, offs[-1])
-        for v in self.vals.values():
-            if v.alias_of is not None:
-                r = _root(v)
-                if r.buf is not None:
-                    shape = v.shape if id(r) not in internal else (chain["batch"], *v.shape[1:])
-                    v.buf = r.buf.view(shape) if r.buf.is_contiguous() else r.buf.reshape(shape)
-        if chain:
-            self._chain = (chain["range"][0], chain["range"][1], chain["parts"], chain["batch"],
-                           [v for v in chain["vals"] if id(_root(v)) not in internal], chain["n"],
-                           [v for v in chain["vals"] if id(_root(v)) in internal and v.buf is not None])
-        self._outputs = []
-        for fv in fetch_vals:
-            if fv.is_const:
-                self._outputs.append(fv.const)
-            else:
-                self._outputs.append(fv)
-
-    # ================================================================== batch-slice chain
-    _CHAIN_KINDS = ("conv", "gemm", "pool", "elementwise", "conv_fp8", "pool_fp8")
-    # persistent kernels that load a resident weight bank per launch
-    _PERSISTENT_IMPLS = ("conv3x3c64", "bottleneck_tail", "bottleneck_chain", "pw_res")
-
-    def _find_chain(self, keep: set) -> dict | None:
-        """The leading run of memory-bound layers that executes once per slice of
-        ``EngineConfig.chain_batch`` images instead of once over the batch (None when off
-        or nothing qualifies).
-
-        Every step of the run is per-image (convs, pools, element-wise) and every tensor it
-        touches is NHWC with at least ``chain_min_hw`` pixels per image — ResNet-50's stem
-        and 56x56 stage 1, where each tensor is 100-400 MB per 256-image batch and every
-        layer streams it from HBM.  Per slice those tensors are 13-51 MB: the values made
-        and consumed inside the run ("internal") get slice-sized buffers reused by every
-        slice, so a layer reads what the previous one just wrote from the Infinity Cache
-        (256 MiB) and a dead intermediate is overwritten there before it is written back.
-        Values entering or leaving the run keep their full buffers and are sliced."""
-        cfg = _cfg()
-        bs = int(getattr(cfg, "chain_batch", 0) or 0)
-        auto = bs < 0
-        if auto:
-            bs = 32
-        if bs == 0 or self._pack is not None or not self.steps or not self.feed_names:
-            return None
-        tn = TensorName.parse(self.feed_names[0])
-        N = self.vals[(tn.name, tn.index)].shape[0] if self.vals[(tn.name, tn.index)].shape else 0
-        if not N or -(-N // bs) < 2:
-            return None
-        min_hw = int(getattr(cfg, "chain_min_hw", 3136))
-
-        edge = bool(getattr(cfg, "chain_edge", False))
-
-        def val_ok(v):
-            if v is None or v.is_const:
-                return True
-            r = _root(v)
-            if v.rows is not None or v.concat_slot is not None or r.concat_slot is not None or r.is_const:
-                return False
-            if len(v.shape) != 4 or v.shape[0] != N:
-                return False
-            return _buf_shape(r)[0] == N
-
-        def step_ok(st):
-            vs = [v for v in list(st.inputs) + list(st.outputs) if v is not None and not v.is_const]
-            if st.kind not in self._CHAIN_KINDS or not vs or not all(val_ok(v) for v in vs):
-                return False
-            if auto and st.meta.get("impl") in self._PERSISTENT_IMPLS:
-                return False  # its per-launch weight prologue outweighs the cache residency (r04_d)
-            big = [v.shape[1] * v.shape[2] >= min_hw for v in vs]
-            # chain_edge: a layer reading the large resolution into a smaller one (the next
-            # stage's stride-2 conv / projection) joins too, so its large input stays internal
-            return any(big) if edge else all(big)
-
-        start = 1 if self.steps[0].kind == "preprocess" else 0  # the head runs per H2D piece
-        best, i = None, start
-        while i < len(self.steps):
-            if not step_ok(self.steps[i]):
-                i += 1
-                continue
-            j = i
-            while j < len(self.steps) and step_ok(self.steps[j]):
-                j += 1
-            if j - i >= 2 and (best is None or j - i > best[1] - best[0]):
-                best = (i, j)
-            i = j
-        if best is None:
-            return None
-        i0, i1 = best
-        vals, touched = [], set()
-        for st in self.steps[i0:i1]:
-            for v in list(st.inputs) + list(st.outputs):
-                while v is not None and not v.is_const:
-                    if all(v is not u for u in vals):
-                        vals.append(v)
-                    touched.add(id(_root(v)))
-                    v = v.alias_of
-        produced = {id(_root(o)) for st in self.steps[i0:i1] for o in st.outputs}
-        used_outside = {id(_root(v)) for k, st in enumerate(self.steps) if not i0 <= k < i1
-                        for v in list(st.inputs) + list(st.outputs) if v is not None and not v.is_const}
-        feeds = {id(_root(self.vals[(TensorName.parse(f).name, TensorName.parse(f).index)])) for f in self.feed_names}
-        internal = {}
-        for v in vals:
-            r = _root(v)
-            k = id(r)
-            if k in produced and k not in used_outside and k not in keep and k not in feeds and r.buf is None:
-                internal[k] = r
-        # a batch that is not a multiple of the slice runs a shorter last slice (the dynamic
-        # batch buckets of 8-image steps): its external rows and slice buffers are narrowed
-        return {"range": (i0, i1), "batch": bs, "parts": -(-N // bs), "n": N, "vals": vals, "touched": touched,
-                "internal": internal}
-
-    def _plan_chain(self, chain: dict, born: dict) -> tuple:
-        """Layout of the chain's slice-sized internal values, planned by the same liveness
-        planner over the chain's own step range (one slice's lifetime): (offsets, total)."""
-        from ..batching.arena import plan_offsets
-
-        i0, i1 = chain["range"]
-        bs = chain["batch"]
-        ts = list(chain["internal"].values())
-        shapes = [(bs, *_buf_shape(t)[1:]) for t in ts]
-        sizes = [_nbytes(s, t.dtype) for s, t in zip(shapes, ts)]
-        first = [born[id(t)] - i0 for t in ts]
-        last = [max(born[id(t)], min(t.last_use, i1 - 1)) - i0 for t in ts]
-        offs, total = plan_offsets(sizes, first, last)
-        return offs, total
-
-    def _bind_chain(self, chain: dict, layout: tuple, slab: torch.Tensor, base: int):
-        """Binds the chain's internal values into their region ``[base, base + total)`` of
-        the activation slab (the subtask arena's shared slab when there is one)."""
-        i0, i1 = chain["range"]
-        bs, parts = chain["batch"], chain["parts"]
-        offs, total = layout
-        ts = list(chain["internal"].values())
-        for t, off in zip(ts, offs):
-            s = (bs, *_buf_shape(t)[1:])
-            nb = _nbytes(s, t.dtype)
-            t.buf = slab[base + off:base + off + nb].view(t.dtype).view(s)
-        self.chain_bytes = total
-        self.chain_layers = i1 - i0
-        LOG.info("batch-slice chain: steps %d-%d (%s .. %s) x %d slices of %d, %d internal values in %.1f MB",
-                 i0, i1 - 1, self.steps[i0].name, self.steps[i1 - 1].name, parts, bs, len(ts), total / 1e6)
-
-    def _run_range(self, lo: int, hi: int, each=None):
-        """Launches steps[lo:hi] (``each(step)`` instead of ``step.fn()`` if given), the
-        batch-slice chain once per slice: the chain's external values are rebound to the
-        slice's rows while its steps launch (eager, or into a capture) and restored after.
-        A plan is driven by one thread at a time (one lane = one stream)."""
-        each = each or (lambda st: st.fn())
-        ch = self._chain
-        if ch is not None and (ch[0] < lo < ch[1] or ch[0] < hi < ch[1]):
-            raise CompileError(f"steps [{lo}, {hi}) cut the batch-slice chain [{ch[0]}, {ch[1]})")
-        i = lo
-        while i < hi:
-            if ch is not None and i == ch[0] and ch[1] <= hi:
-                for p in range(ch[2]):
-                    self._run_chain_slice(p, each)
-                i = ch[1]
-                continue
-            each(self.steps[i])
-            i += 1
-
-    def _run_chain_slice(self, p: int, each=None):
-        """The chain's steps for slice ``p`` (images [p*bs, (p+1)*bs)), its external values
-        rebound to the slice's rows while they launch."""
-        each = each or (lambda st: st.fn())
-        i0, i1, parts, bs, ext, n, ints = self._chain
-        lo, hi = p * bs, min(n, (p + 1) * bs)
-        full = [(v, v.buf, True) for v in ext if v.buf is not None]
-        if hi - lo < bs:  # the short last slice: the slice-sized internals' leading rows
-            full += [(v, v.buf, False) for v in ints]
-        try:
-            for v, b, external in full:
-                v.buf = b[lo:hi] if external else b[:hi - lo]
-            for st in self.steps[i0:i1]:
-                each(st)
-        finally:
-            for v, b, _ in full:
-                v.buf = b
-
-    def _persistent(self, shape, dtype) -> torch.Tensor:
-        """A buffer outside the shared slab (plan inputs, fetched outputs)."""
-        if self.arena is not None:
-            return self.arena.alloc(tuple(shape), dtype)
-        return torch.empty(tuple(shape), dtype=dtype, device=self.device)
-
-    def _dev(self, t: torch.Tensor, dtype=None) -> torch.Tensor:
-        """A baked-in weight on the device; identical weights of a subtask's bucket plans
-        are stored once in its arena."""
-        t = t.to(dtype) if dtype is not None else t
-        if self.arena is not None:
-            return self.arena.intern(t.contiguous())
-        return t.to(self.device).contiguous()
-
-    # ================================================================== execution
-    def _run_steps(self):
-        if not (self._debug_sync or self._poison_after and tracing.debug_poison()):
-            self._run_range(0, len(self.steps))
-            return
-        poison = tracing.debug_poison()
-        index = {id(s): i for i, s in enumerate(self.steps)}
-        ch = self._chain
-
-        def each(s):
-            i = index[id(s)]
-            s.fn()
-            if self._debug_sync and self.device.type == "cuda":
-                try:
-                    torch.cuda.synchronize(self.device)
-                except RuntimeError as e:
-                    raise RuntimeError(f"step {i} ({s.kind} {s.name}) failed: {e}") from e
-            if poison and not (ch is not None and ch[0] <= i < ch[1]):  # chain buffers: live per slice
-                for b in self._poison_after.get(i, ()):
-                    b.view(-1).view(torch.uint8).fill_(0xFF)  # NaN in bf16/fp32, 0xFF in e4m3 = NaN
-
-        self._run_range(0, len(self.steps), each)
-
-    def profile(self, feeds: dict | None = None):
-        """One eager run with a HIP event pair around every launch: a ``RunMetadata``
-        whose ``NodeExecStats`` carry the per-step device time (``timeline_label`` = kind)
-        — the compiled counterpart of ``Session.run(run_metadata=True)``."""
-        from ..proto.messages import DeviceStepStats, NodeExecStats, RunMetadata, StepStats
-
-        for k, v in (feeds or {}).items():
-            self.input_buffer(k).copy_(v)
-        stats = []
-        index = {id(s): i for i, s in enumerate(self.steps)}
-        if self.device.type == "cuda":
-            evs = [[] for _ in self.steps]  # a chain step launches once per batch slice
-
-            def each(s):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                s.fn()
-                e1.record()
-                evs[index[id(s)]].append((e0, e1))
-
-            self._run_range(0, len(self.steps), each)
-            torch.cuda.synchronize(self.device)
-            times = [sum(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev) for ev in evs]
-        else:
-            import time
-
-            times = [0.0] * len(self.steps)
-
-            def each(s):
-                t0 = time.perf_counter()
-                s.fn()
-                times[index[id(s)]] += (time.perf_counter() - t0) * 1e6
-
-            self._run_range(0, len(self.steps), each)
-        t = 0
-        for s, us in zip(self.steps, times):
-            stats.append(NodeExecStats(node_name=s.name, all_start_micros=int(t), op_end_rel_micros=int(us),
-                                       all_end_rel_micros=int(us), timeline_label=s.kind))
-            t += us
-        return RunMetadata(step_stats=StepStats(dev_stats=[DeviceStepStats(device=str(self.device),
-                                                                           node_stats=stats)]))
-
-    def _capture(self):
-        with tracing.capture_lock():  # warm-up + device sync + capture: no sibling capture in between
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._run_steps()
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with tracing.graph_capture(g):
-                self._run_steps()
-            self._graph_obj = g
-            self._head = self._head_feed_step()
-            if self._head is not None:
-                # the two graphs of a plan never replay concurrently (one lane = one stream):
-                # the tail graph shares the full graph's private memory pool
-                gt = torch.cuda.CUDAGraph()
-                with tracing.graph_capture(gt, pool=g.pool()):
-                    self._run_range(1, len(self.steps))
-                self._graph_tail = gt
-
-    def _head_feed_step(self):
-        """``(feed, step)`` when the first step is the fused preprocess kernel and its input is
-        a feed buffer no other step and no fetch reads; else None."""
-        if not self.steps or self.steps[0].kind != "preprocess" or len(self.steps[0].inputs) != 1:
-            return None
-        st = self.steps[0]
-        x = st.inputs[0]
-        if x.buf is None:
-            return None
-        feeds = [k for k, b in self._input_bufs.items() if b.data_ptr() == x.buf.data_ptr()]
-        if len(feeds) != 1:
-            return None
-        # compare alias roots (a Reshape of the feed is an alias Val sharing its buffer) and
-        # buffer addresses: any other reader of the raw feed needs the input_buffer copy
-        rx, ptr = _root(x), x.buf.data_ptr()
-
-        def reads_feed(v):
-            return v is not None and (_root(v) is rx or (v.buf is not None and v.buf.data_ptr() == ptr))
-
-        if any(reads_feed(i) for t in self.steps[1:] for i in t.inputs) or any(reads_feed(o) for o in self._outputs):
-            return None
-        return feeds[0], st
-
-    def input_buffer(self, feed: str) -> torch.Tensor:
-        return self._input_bufs[str(TensorName.parse(feed))]
-
-    def replay_from(self, feed: str, src: torch.Tensor):
-        """``input_buffer(feed).copy_(src); replay()`` without the copy when it can: if the
-        plan starts with the preprocess kernel on ``feed``, that kernel is launched (outside
-        the graph) straight on ``src`` — e.g. the runner's H2D staging slot — and the graph
-        of the remaining steps is replayed.  Saves one D2D pass over the raw uint8 batch
-        (50 MB for ResNet-50 at B=256) per micro-batch."""
-        h = self._head
-        buf = self.input_buffer(feed)
-        if (h is None or self._graph_tail is None or h[0] != str(TensorName.parse(feed))
-                or src.shape != buf.shape or src.dtype != buf.dtype or src.device != buf.device
-                or not src.is_contiguous()):
-            buf.copy_(src, non_blocking=True)
-            self.replay()
-            return
-        h[1].fn(x=types.SimpleNamespace(buf=src))
-        self._graph_tail.replay()
-
-    def replay_from_chunks(self, feed: str, src: torch.Tensor, chunks, wait) -> bool:
-        """``replay_from`` for a batch that reaches the device in pieces: the head
-        preprocess kernel runs per piece ``chunks[i] = (lo, hi)`` right after ``wait(i)``
-        (the current stream waits for that piece's H2D), so the GPU starts on the first
-        records while the rest are still being gathered / copied; then the graph of the
-        remaining steps.  False (nothing launched) when the plan has no such head."""
-        if not self.head_pieces_ok(feed, src):
-            return False
-        for i, (lo, hi) in enumerate(chunks):
-            wait(i)
-            self.launch_head_piece(src, lo, hi)
-        self.replay_tail()
-        return True
-
-    def head_pieces_ok(self, feed: str, src: torch.Tensor) -> bool:
-        """The plan starts with a head kernel on ``feed`` that can run per piece of ``src``
-        (``launch_head_piece``), the rest of the plan being one captured graph
-        (``replay_tail``): the pipelined runner launches each piece's head right after that
-        piece's H2D, interleaved with the host gather of the next piece."""
-        h = self._head
-        buf = self.input_buffer(feed)
-        return not (h is None or self._graph_tail is None or h[0] != str(TensorName.parse(feed))
-                    or src.shape != buf.shape or src.dtype != buf.dtype or src.device != buf.device
-                    or not src.is_contiguous() or len(h[1].outputs) != 1)
-
-    def launch_head_piece(self, src: torch.Tensor, lo: int, hi: int) -> None:
-        st = self._head[1]
-        out = _root(st.outputs[0]).buf
-        st.fn(x=types.SimpleNamespace(buf=src[lo:hi]), out=types.SimpleNamespace(buf=out[lo:hi]))
-
-    def replay_tail(self) -> None:
-        self._graph_tail.replay()
-
-    def replay(self):
-        """Runs the plan on the current input buffers (no host synchronisation)."""
-        if self._graph_obj is not None:
-            self._graph_obj.replay()
-        else:
-            self._run_steps()
-
-    def __call__(self, feeds: dict | None = None, copy_outputs: bool = True, cast_outputs: bool = True):
-        for k, v in (feeds or {}).items():
-            buf = self.input_buffer(k)
-            if isinstance(v, StringTensor):
-                raise CompileError("STRING feeds are not supported in compiled plans")
-            buf.copy_(v, non_blocking=True)
-        self.replay()
-        outs = []
-        for o in self._outputs:
-            if isinstance(o, Val):
-                b = _view(o)
-                if o.qscale is not None:
-                    b = F8.from_fp8_bytes(b) * _eff_scale(o)
-                elif cast_outputs and b.dtype == torch.bfloat16:
-                    b = b.float()
-                elif copy_outputs:
-                    b = b.clone()
-                outs.append(b)
-            else:
-                outs.append(o)
-        return outs
-
-    def output_tensors(self) -> list:
-        """The static device tensors holding the fetched values (valid after replay)."""
-        return [_view(o) if isinstance(o, Val) else o for o in self._outputs]
 
     def param_bytes(self) -> int:
         return sum(p.numel() * p.element_size() for p in self.params)

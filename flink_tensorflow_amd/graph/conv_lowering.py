@@ -17,7 +17,6 @@ import torch
 
 from ..ops import fp8 as F8
 from ..ops import kernels as K
-from ..types.names import TensorName
 from .graph import Node
 from .ops_nn import same_pads
 from .plan import CompileError, Val, _cfg, _coff, _eff_scale, _root, _target, _view
@@ -421,14 +420,13 @@ class ConvLowering:
         xu = pp["x"]
         osc = _eff_scale(out) if out.qscale is not None else None
 
-        def run_u(x=xu, out=out, w_arr=w_arr, b_dev=b_dev, bn=bn, osc=osc, mean=pp["mean"], std=pp["std"],
-                  pads=s.pads):
-            K.conv2d_direct_u8s2d(x.buf, w_arr, s.kernel, s.cout, b_dev, pads, s.act, mean, std, out=out.buf,
+        def head(src, dst):
+            K.conv2d_direct_u8s2d(src, w_arr, s.kernel, s.cout, b_dev, s.pads, s.act, pp["mean"], pp["std"], out=dst,
                                   bn=bn, out_scale=osc)
 
         # kind "preprocess": still the plan's head, launched per H2D piece by the runner
-        self._emit(c.node.name, "preprocess", run_u, [xu], [out],
-                   {"impl": "dconv_u8s2d", "conv_out": tuple(out.shape)})
+        self._emit(c.node.name, "preprocess", lambda: head(xu.buf, out.buf), [xu], [out],
+                   {"impl": "dconv_u8s2d", "conv_out": tuple(out.shape)}, head=head)
         self.stats["fused_preprocess"] = 1
         self._finish_conv(c.last, c.absorbed, out)
         return True
@@ -520,12 +518,9 @@ class ConvLowering:
         prod = [st for st in self.steps if any(o is res_val for o in st.outputs)]
         if len(prod) != 1 or "shortcut" not in prod[0].meta or res_val.concat_slot is not None:
             return False
-        for (n, _), v in self.vals.items():  # the projection feeds only this Add
-            if v is res_val:
-                if any(TensorName.parse(f).name == n for f in self.fetch_names):
-                    return False
-                if any(k != c.add_node.name and k not in self._fused for k in self.cons.get(n, [])):
-                    return False
+        readers = self._readers(res_val)  # the projection feeds only this Add
+        if readers is None or any(k != c.add_node.name and k not in self._fused for k in readers):
+            return False
         sc = prod[0].meta["shortcut"]
         x2 = sc["x"]
         s2 = sc["stride"]
@@ -686,7 +681,7 @@ class ConvLowering:
         if (out.qscale is not None or out.dtype != torch.bfloat16) if not fp8 else \
                 (out.qscale is None or out.dtype != torch.uint8):
             return None
-        if any(TensorName.parse(f).name == last.name for f in self.fetch_names):
+        if self._fetched(last.name):
             return None
         cons = [c for c in self.cons.get(last.name, []) if c not in self._fused]
         if len(cons) != 1 or self.graph[cons[0]].op != "MaxPool":
@@ -791,14 +786,8 @@ class ConvLowering:
     def _s2d_ok(self, x: Val, node: Node, C, sh, sw, dh, dw, pt, pl, H, W) -> bool:
         if x.pre_cfg is None or C != 3 or (sh, sw) != (2, 2) or (dh, dw) != (1, 1) or pt % 2 or pl % 2:
             return False
-        chain = x.pre_chain
-        users = set()
-        for (n, _), v in self.vals.items():
-            if v is x:
-                if any(TensorName.parse(f).name == n for f in self.fetch_names):
-                    return False
-                users.update(c for c in self.cons.get(n, []) if c not in chain)
-        return users == {node.name}
+        users = self._readers(x)
+        return users is not None and users - x.pre_chain == {node.name}
 
     def _ensure_padded(self, x: Val, cin_pad: int, name: str) -> Val:
         if x.qscale is not None:
@@ -1016,7 +1005,7 @@ class ConvLowering:
 
     # ---- post-passes over the fused block tails
     def _fetched_roots(self) -> set:
-        return {id(_root(self.vals[(TensorName.parse(f).name, TensorName.parse(f).index)])) for f in self.fetch_names}
+        return {id(_root(self._val_of(f))) for f in self.fetch_names}
 
     def _chain_tails(self):
         """ResNet stage 1's residual stream by recomputation (kernels/bottleneck_chain.hip):

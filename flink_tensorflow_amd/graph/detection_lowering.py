@@ -48,10 +48,10 @@ _ADD = ("Add", "AddV2")
 
 
 class DetectionLowering:
-    """Mixin of ``CompiledFunction`` (uses its graph, ``cons``, ``vals`` and emitters).  It also
-    uses the graph helpers of the ``TransformerLowering`` mixin next to it: ``_fetched``,
-    ``_consumers``, ``_is_const_node``, ``_const_of`` and ``_add_group`` (a matched decode is a
-    ``_groups`` entry of kind ``"decode"``, dispatched by ``_lower_group``)."""
+    """Mixin of ``CompiledFunction`` (uses its graph, ``cons``, ``vals``, ``_fetched`` and emitters).
+    It also uses the graph helpers of the ``TransformerLowering`` mixin next to it: ``_consumers``,
+    ``_is_const_node``, ``_const_of`` and ``_add_group`` (a matched decode is a ``_groups`` entry
+    of kind ``"decode"``, dispatched by ``_lower_group``)."""
 
     # ------------------------------------------------------------------ matching
     def _prematch_detection(self):

@@ -1,6 +1,7 @@
 """The plan vocabulary shared by the graph compiler and its lowering mixins: symbolic
-values (``Val``), launch steps (``Step``), ``CompileError`` and the helpers that map a value
-to its physical buffer.  A leaf module: it imports nothing from the compiler."""
+values (``Val``), launch steps (``Step``), the batch-slice chain record (``Chain``),
+``CompileError`` and the helpers that map a value to its physical buffer.  A leaf module: it
+imports nothing from the compiler."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -32,6 +33,7 @@ class Val:
     alias_of: "Val | None" = None
     last_use: int = -1
     concat_slot: tuple | None = None  # (target Val, channel offset) for concat-by-stride-write
+    concat_children: list | None = None  # on that target: the branch Vals written into its slices
     qscale: float | None = None  # fp8 e4m3 storage (uint8 buffer) with this per-tensor scale
     # token-packed plans (``token_capacity``): "packed" = one row per real token (the plan's
     # token capacity T rows), "cls" = one row per sequence (its first token); ``shape`` is
@@ -60,6 +62,9 @@ class Val:
     # absorbed ``Transpose`` that only a ``BlockLSTM`` reads, without a step or a buffer;
     # ``tm_of`` is the batch-major ``[B, T, I]`` source Val, read in place through strides
     tm_of: "Val | None" = None
+    # dense prediction heads: a ``ResizeBilinear`` result without a step or a buffer, read only by an
+    # ``ArgMax`` that interpolates on the fly: (source Val, align_corners, half_pixel_centers)
+    resize_of: tuple | None = None
 
     @property
     def is_const(self):
@@ -74,6 +79,25 @@ class Step:
     inputs: list = field(default_factory=list)
     outputs: list = field(default_factory=list)
     meta: dict = field(default_factory=dict)
+    # launches this step reading ``src`` and writing ``dst`` instead of its bound buffers: the plan's head only
+    head: Callable[[torch.Tensor, torch.Tensor], None] | None = None
+
+
+@dataclass
+class Chain:
+    """The batch-slice chain of a plan (``PlanMemory._find_chain``): steps ``range`` run once
+    per slice of ``batch`` images, ``parts`` times over the ``n`` images of the batch."""
+
+    range: tuple    # (first step, end step)
+    batch: int      # images per slice
+    parts: int      # number of slices; a short last one when ``batch`` does not divide ``n`` (dynamic batch buckets)
+    n: int          # images in the batch
+    vals: list      # every value (alias Vals included) the chain's steps read or write
+    touched: set    # ids of the roots of ``vals``: they live across the whole chain
+    internal: dict  # id -> root Val made and consumed inside the chain: one slice-sized buffer
+    # filled at bind time, rebound per slice by ``PlanRunner._run_chain_slice``:
+    external: list = field(default_factory=list)  # the values on full-batch buffers, sliced ``[lo:hi]``
+    bound: list = field(default_factory=list)     # the bound internal values, narrowed for a short last slice
 
 
 def _buf_shape(r: Val) -> tuple:

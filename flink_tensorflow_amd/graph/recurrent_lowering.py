@@ -41,13 +41,12 @@ from __future__ import annotations
 import torch
 
 from ..ops import kernels as K
-from ..types.names import TensorName
 from .plan import Val, _view
 
 
 class RecurrentLowering:
-    """Mixin of ``CompiledFunction`` (uses its graph, ``cons``, ``vals`` and emitters, and the
-    graph helpers ``_const_of`` / ``_fetched`` of the ``TransformerLowering`` mixin)."""
+    """Mixin of ``CompiledFunction`` (uses its graph, ``cons``, ``vals``, ``_fetched`` and emitters,
+    and the graph helper ``_const_of`` of the ``TransformerLowering`` mixin)."""
 
     # ------------------------------------------------------------------ graph helpers
     def _is_tb_transpose(self, node) -> bool:
@@ -65,7 +64,7 @@ class RecurrentLowering:
         return out
 
     def _out_fetched(self, name: str, k: int) -> bool:
-        return any((t.name, t.index) == (name, k) for t in map(TensorName.parse, self.fetch_names))
+        return f"{name}:{k}" in self.fetch_names  # they are normalised to ``node:index``
 
     def _is_last_step_slice(self, node, shape) -> bool:
         """``x[T - 1]`` / ``x[-1]`` of a ``[T, B, H]`` value as a StridedSlice: axis 0 shrunk,

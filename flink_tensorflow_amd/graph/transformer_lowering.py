@@ -60,16 +60,8 @@ class TransformerLowering:
         return list(self.cons.get(name, []))
 
     def _only_consumer(self, name, op_types):
-        c = self._consumers(name)
-        if len(c) != 1 or self._fetched(name):
-            return None
-        n = self.graph[c[0]]
-        return n if n.op in op_types else None
-
-    def _fetched(self, name):
-        from ..types.names import TensorName
-
-        return any(TensorName.parse(f).name == name for f in self.fetch_names)
+        n = self._single_consumer(name)
+        return n if n is not None and n.op in op_types else None
 
     def _is_const_node(self, src) -> bool:
         """True when ``src`` depends only on constants (checked structurally)."""
@@ -297,9 +289,8 @@ class TransformerLowering:
         if len(embs) != 1 or not attns:
             raise CompileError("token packing needs one embedding group and fused attention")
         ids_src = embs[0]["ids"]
-        feed = next((f for f in self.feed_names if (TensorName.parse(f).name, TensorName.parse(f).index) == ids_src),
-                    None)
-        if feed is None:
+        feed = f"{ids_src[0]}:{ids_src[1]}"  # feed names are normalised to ``node:index``
+        if feed not in self.feed_names:
             raise CompileError("token packing needs the embedding ids to be a feed")
         shape, _ = self.feed_specs[feed]
         if len(shape) != 2:

@@ -1,6 +1,6 @@
 """Batch-slice chain (``EngineConfig.chain_batch``): the plan's leading run of large-activation
 layers runs once per slice of images with slice-sized intermediates; outputs must equal the
-unsliced plan's (graph/compiler.py ``_find_chain``)."""
+unsliced plan's (graph/plan_memory.py ``_find_chain``)."""
 import pytest
 import torch
 
@@ -30,10 +30,10 @@ def test_chain_host_matches_unsliced(small_resnet):
     imgs = torch.randint(0, 256, (4, 72, 72, 3), dtype=torch.uint8)
     base, ch = _plans(small_resnet, "cpu", 4, 2)
     c = ch._chain
-    assert c is not None and c[2] == 2 and c[3] == 2
+    assert c is not None and c.parts == 2 and c.batch == 2
     # every chain step is a stage-1 (18x18) or stem layer; the slice buffers are a fraction
     # of the batch's activations
-    names = [s.name for s in ch.steps[c[0]:c[1]]]
+    names = [s.name for s in ch.steps[slice(*c.range)]]
     assert all(n.startswith(("conv1", "pool1", "block1/")) for n in names), names
     assert len(names) >= 5 and ch.chain_bytes > 0
     a = base({"images:0": imgs})
@@ -52,7 +52,7 @@ def test_chain_edge_takes_the_stride2_readers(small_resnet):
         base = CompiledFunction(small_resnet, feeds, ["logits:0"], "cpu", strict=True)
     with config.override(chain_batch=2, chain_min_hw=3136, chain_edge=True):
         ch = CompiledFunction(small_resnet, feeds, ["logits:0"], "cpu", strict=True)
-    names = [s.name for s in ch.steps[ch._chain[0]:ch._chain[1]]]
+    names = [s.name for s in ch.steps[slice(*ch._chain.range)]]
     # the stage-2 entry 3x3/s2 conv reads the 56x56 tail output: it joins the chain, and
     # that 56x56 tensor becomes a slice-sized internal value
     assert "block2/unit1/conv2/Conv2D" in names
@@ -74,10 +74,10 @@ def test_chain_auto_takes_the_inception_stem_not_resnet_stage1(small_resnet):
     # (the GPU plan fuses ResNet's stem conv and max pool into one launch, so nothing chains;
     # the host plan may chain those two steps, never stage 1)
     rc = getattr(rn, "_chain", None)
-    assert rc is None or {s.name for s in rn.steps[rc[0]:rc[1]]} <= {"conv1/Conv2D", "pool1"}
+    assert rc is None or {s.name for s in rn.steps[slice(*rc.range)]} <= {"conv1/Conv2D", "pool1"}
     c = inc._chain
-    assert c is not None and c[2] == 2 and c[3] == 32
-    names = [s.name for s in inc.steps[c[0]:c[1]]]
+    assert c is not None and c.parts == 2 and c.batch == 32
+    names = [s.name for s in inc.steps[slice(*c.range)]]
     assert names[0].endswith("Conv2d_1a_3x3/Conv2D") and names[-1].endswith("MaxPool_5a_3x3"), names
 
 
@@ -87,7 +87,7 @@ def test_chain_short_last_slice(small_resnet):
     imgs = torch.randint(0, 256, (5, 72, 72, 3), dtype=torch.uint8)
     base, ch = _plans(small_resnet, "cpu", 5, 2)
     c = ch._chain
-    assert c is not None and c[2] == 3 and c[3] == 2
+    assert c is not None and c.parts == 3 and c.batch == 2
     torch.testing.assert_close(ch({"images:0": imgs})[0], base({"images:0": imgs})[0], rtol=0, atol=1e-5)
     with config.override(chain_batch=8, chain_min_hw=3136):  # one slice: nothing to chain
         plan = CompiledFunction(small_resnet, {"images:0": ((4, 72, 72, 3), "UINT8")}, ["logits:0"], "cpu",
@@ -112,3 +112,26 @@ def test_chain_gpu_matches_unsliced(small_resnet):
     assert ch.replay_from_chunks("images:0", src, pieces, lambda i: None)
     torch.cuda.synchronize()
     assert torch.equal(ch.output_tensors()[0].float(), b[0])
+
+
+@pytest.mark.gpu
+def test_folded_head_per_piece_gpu():
+    """The stem conv that absorbed the preprocess kernel (``dconv_u8s2d``) is the plan's head:
+    launched per H2D piece on the caller's buffer, then the tail graph.  Every image is computed
+    on its own, so the pieces give the full replay's outputs bit for bit."""
+    from flink_tensorflow_amd.models.zoo.inception_v3 import inception_v3_graph_def
+
+    dev = torch.device("cuda", 0)
+    g = Graph.from_graph_def(inception_v3_graph_def(image_hw=(75, 75), out_hw=(75, 75)))
+    plan = CompiledFunction(g, {"images:0": ((4, 75, 75, 3), "UINT8")}, ["logits:0"], dev, strict=True)
+    assert plan.summary()["fused_preprocess"] == 1
+    src = torch.randint(0, 256, (4, 75, 75, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(5)).to(dev)
+    ref = plan({"images:0": src}, cast_outputs=False)
+    other = 255 - src
+    stale = plan({"images:0": other}, cast_outputs=False)  # the outputs and the input buffer now hold other images
+    assert not torch.equal(stale[0], ref[0])
+    assert plan.replay_from_chunks("images:0", src, [(0, 1), (1, 4)], lambda i: None)
+    torch.cuda.synchronize()
+    got = plan.output_tensors()
+    assert len(got) == len(ref) and all(torch.equal(a, b) for a, b in zip(got, ref))
+    assert torch.equal(plan.input_buffer("images:0"), other)

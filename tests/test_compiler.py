@@ -186,6 +186,26 @@ def test_replay_from_staging_buffer_gpu(small_resnet):
     assert torch.equal(plan.output_tensors()[0].float(), ref.float())
 
 
+def test_head_launcher_per_piece_host(small_resnet):
+    """The head step's ``head(src, dst)`` launched on two pieces of a caller's tensor, then the
+    other steps: the plain call's outputs bit for bit, and the plan's input buffer is not read."""
+    imgs = torch.randint(0, 256, (3, 72, 72, 3), dtype=torch.uint8)
+    plan = CompiledFunction(small_resnet, {"images:0": ((3, 72, 72, 3), "UINT8")}, ["logits:0", "top_k:1"], "cpu",
+                            strict=True)
+    ref = plan({"images:0": imgs})
+    other = 255 - imgs
+    assert not torch.equal(plan({"images:0": other})[0], ref[0])  # buffers and outputs now hold other images
+    feed, st = plan._head_feed_step()
+    assert feed == "images:0" and st is plan.steps[0] and st.head is not None
+    src = imgs.clone()
+    for lo, hi in [(0, 1), (1, 3)]:
+        st.head(src[lo:hi], st.outputs[0].buf[lo:hi])
+    plan._run_range(1, len(plan.steps))
+    got = plan.output_tensors()
+    assert torch.equal(got[0].float(), ref[0]) and torch.equal(got[1], ref[1])
+    assert torch.equal(plan.input_buffer("images:0"), other)
+
+
 def test_head_bypass_refused_when_the_feed_has_other_readers():
     """``replay_from`` may skip the input copy only if the preprocess step is the raw feed's
     sole reader: a fetch of the feed itself, or of a Reshape alias of it, keeps the copy."""
