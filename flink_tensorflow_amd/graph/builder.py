@@ -256,6 +256,30 @@ class GraphBuilder:
                       forget_bias=float(forget_bias), cell_clip=float(cell_clip), use_peephole=peep, T=DataType.FLOAT)
         return out.split(":")[0]
 
+    def audio_spectrogram(self, x, window_size, stride, magnitude_squared=False, name=None) -> str:
+        """``AudioSpectrogram`` of ``x [samples, channels]``: ``[channels, frames, N/2 + 1]``."""
+        return self.op("AudioSpectrogram", [x], name=name, window_size=int(window_size), stride=int(stride),
+                       magnitude_squared=bool(magnitude_squared))
+
+    def mfcc(self, spectrogram, sample_rate, upper_frequency_limit=4000.0, lower_frequency_limit=20.0,
+             filterbank_channel_count=40, dct_coefficient_count=13, name=None) -> str:
+        """``Mfcc`` of a squared-magnitude spectrogram; ``sample_rate`` is a number or a tensor name."""
+        nm = name or "Mfcc"
+        if not isinstance(sample_rate, str):
+            sample_rate = self.constant(f"{nm}/sample_rate", np.asarray(sample_rate, dtype=np.int32))
+        return self.op("Mfcc", [spectrogram, sample_rate], name=name,
+                       upper_frequency_limit=float(upper_frequency_limit),
+                       lower_frequency_limit=float(lower_frequency_limit),
+                       filterbank_channel_count=int(filterbank_channel_count),
+                       dct_coefficient_count=int(dct_coefficient_count))
+
+    def decode_wav(self, contents, desired_channels=-1, desired_samples=-1, name=None) -> str:
+        """``DecodeWav``.  Returns the node NAME: ``name:0`` is the audio ``[samples, channels]``,
+        ``name:1`` the sample rate."""
+        out = self.op("DecodeWav", [contents], name=name, desired_channels=int(desired_channels),
+                      desired_samples=int(desired_samples))
+        return out.split(":")[0]
+
     def top_k(self, x, k, name=None) -> str:
         kk = self.constant(f"{(name or 'TopKV2')}/k", np.asarray(k, dtype=np.int32))
         return self.op("TopKV2", [x, kk], name=name, sorted=True)

@@ -24,6 +24,9 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``[Transpose] → BlockLSTM → [Transpose | last-step StridedSlice]`` → one projection
      ``gemm`` step plus one ``lstm`` step that walks the whole sequence (kernels/lstm.hip,
      ``recurrent_lowering.py``); the layout ops emit nothing;
+   * ``[Cast(INT16) → Mul|RealDiv] → [Transpose] → AudioSpectrogram → Mfcc → [Reshape]`` → one
+     ``mfcc`` step from PCM to coefficients (kernels/audio.hip, ``audio_lowering.py``); a lone
+     ``AudioSpectrogram`` → one ``spectrogram`` step;
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -37,12 +40,13 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is eight modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+The compiler is nine modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
 map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
 pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
 ``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
 mixin: box decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering`` mixin: ``BlockLSTM`` and the layout
-ops around it), ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
+ops around it), ``audio_lowering.py`` (the ``AudioLowering`` mixin: the spectrogram / MFCC front end and the
+ops it absorbs), ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
 ``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
 bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
 
@@ -72,6 +76,7 @@ from ..types.dtypes import DataType
 from ..types.names import TensorName
 from ..utils import tracing
 from . import ops_core  # noqa: F401
+from .audio_lowering import AudioLowering
 from .conv_lowering import _ACTS, ConvLowering
 from .detection_lowering import _UNPADDED_NMS, DetectionLowering
 from .graph import Graph, Node
@@ -103,7 +108,7 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, ConvLowering, PlanMemory, PlanRunner):
+class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering, ConvLowering, PlanMemory, PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -410,6 +415,8 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         if op == "BlockLSTM":
             return self._lower_block_lstm(node)
         if op == "Transpose" and self._lower_tb_transpose(node):
+            return
+        if op in ("Cast", "Transpose", "AudioSpectrogram") and self._lower_audio_from(node):
             return
         if op in ("MaxPool", "AvgPool"):
             return self._lower_pool(node)

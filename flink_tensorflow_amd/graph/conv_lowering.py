@@ -73,12 +73,15 @@ class ConvSite:
         return not self.s2d and self.cin_phys == self.cin
 
 
-def _dconv_ok(on_gpu, cin_phys, kernel, stride, dil, es, residual, act) -> bool:
+def _dconv_ok(on_gpu, cin_phys, kernel, stride, dil, es, residual, act, bn=64) -> bool:
     """Direct LDS conv for narrow layers (input row <= 32 B: RGB stems, Inception's
     32-channel fp8 layers); measured faster there by bench/dconv_tune.py, slower for
     wider inputs, which stay on the implicit GEMM."""
     return (on_gpu and not residual and act in _PLAIN_ACTS
-            and cin_phys * es <= 32 and K.dconv_eligible(cin_phys, *kernel, stride, dil, es))
+            and cin_phys * es <= 32 and K.dconv_eligible(cin_phys, *kernel, stride, dil, es, bn))
+
+
+IGEMM_MAX_TAPS = 64  # the implicit GEMM keeps the in-image taps of a pixel in one 64-bit mask
 
 
 # the choices tried after the graph-structural fusions of a residual 1x1 conv
@@ -91,6 +94,11 @@ def select_conv_kernel(s: ConvSite) -> str:
     ``gemm_pp``, then (after the fusions of ``AFTER_FUSIONS``) ``pw_res``, ``conv_lite``
     and the register-staged implicit GEMM ``igemm``, which takes everything."""
     if _dconv_ok(s.on_gpu, s.cin_phys, s.kernel, s.stride, s.dil, 2, s.residual, s.act):
+        return "dconv"
+    if s.kernel[0] * s.kernel[1] > IGEMM_MAX_TAPS and _dconv_ok(s.on_gpu, s.cin_phys, s.kernel, s.stride, s.dil, 2,
+                                                                s.residual, s.act, bn=32):
+        # a filter the implicit GEMM cannot take (the keyword spotter's 20 x 8 first conv over
+        # one padded input channel) whose bank fits LDS in 32-channel tiles only
         return "dconv"
     if (not s.residual and not s.out_fp8 and s.unpadded_cin and s.conv3x3c64_kernel
             and K.conv3x3_c64_eligible(s.x_shape, (s.cout, *s.kernel, s.cin_phys), s.stride, s.pads, s.dil, None,
@@ -379,7 +387,7 @@ class ConvLowering:
     def _emit_dconv(self, c: _ConvJob):
         s, out = c.site, c.out
         Cout, conv_out = s.cout, tuple(c.out.shape)
-        bn = 64 if Cout >= 64 else 32
+        bn = 64 if Cout >= 64 and K.dconv_eligible(s.cin_phys, *s.kernel, s.stride, s.dil, 2, 64) else 32
         w_arr = self._dev(K.dconv_bf16_weight_bytes(c.w_ohwi, bn))
         b_dev = c.b_dev if c.b_dev is not None else torch.zeros(Cout, dtype=torch.float32, device=self.device)
         self.params += [w_arr, b_dev]

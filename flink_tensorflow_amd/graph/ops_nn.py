@@ -425,3 +425,190 @@ def block_lstm(seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b, forget_bias
 def _block_lstm(ctx, node, seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b):
     return block_lstm(seq_len_max, x, cs_prev, h_prev, w, wci, wcf, wco, b, float(node.attr("forget_bias", 1.0)),
                       float(node.attr("cell_clip", 3.0)), bool(node.attr("use_peephole", False)))
+
+
+# ------------------------------------------------------------------ audio front end
+def spectrogram_fft_length(window_size: int) -> int:
+    """The smallest power of two ``>= window_size`` (TF ``Spectrogram::Initialize``)."""
+    n = 1
+    while n < window_size:
+        n *= 2
+    return n
+
+
+def spectrogram_frames(samples: int, window_size: int, stride: int) -> int:
+    return 1 + (samples - window_size) // stride if samples >= window_size else 0
+
+
+def audio_spectrogram(x, window_size: int, stride: int, magnitude_squared: bool = False):
+    """TF ``AudioSpectrogram``: ``x [S, Ch]`` float to ``[Ch, F, N/2 + 1]`` float32, with ``N`` the
+    smallest power of two ``>= window_size`` and ``F = 1 + (S - window_size) // stride`` frames
+    (0 when ``S < window_size``).  Frame ``f`` is samples ``[f stride, f stride + window_size)``
+    times the periodic Hann window ``0.5 - 0.5 cos(2 pi n / window_size)``, zero-padded to ``N``;
+    the output is ``re^2 + im^2`` of its real DFT, or the square root of that when
+    ``magnitude_squared`` is false.  Computed in float64, as TF does."""
+    if x.dim() != 2:
+        raise ValueError(f"AudioSpectrogram: input {tuple(x.shape)} is not [samples, channels]")
+    window_size, stride = int(window_size), int(stride)
+    if window_size < 2 or stride < 1:
+        raise ValueError(f"AudioSpectrogram: window_size={window_size} (>= 2) / stride={stride} (>= 1)")
+    S, Ch = x.shape
+    N = spectrogram_fft_length(window_size)
+    F_ = spectrogram_frames(S, window_size, stride)
+    if F_ == 0:
+        return torch.zeros((Ch, 0, N // 2 + 1), dtype=torch.float32, device=x.device)
+    n = torch.arange(window_size, dtype=torch.float64, device=x.device)
+    hann = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n / window_size)
+    xt = x.to(torch.float64).t().contiguous()  # [Ch, S]
+    frames = xt[:, :(F_ - 1) * stride + window_size].unfold(1, window_size, stride) * hann  # [Ch, F, window]
+    z = torch.fft.rfft(frames, n=N, dim=-1)
+    p = z.real * z.real + z.imag * z.imag
+    return (p if magnitude_squared else p.sqrt()).to(torch.float32)
+
+
+def mel_filterbank(bins: int, sample_rate: float, lower: float, upper: float, channels: int):
+    """TF's ``MfccMelFilterbank`` for spectrogram rows of ``bins`` values, as float64 numpy:
+    ``(start, end, band [bins] int, weight [bins])``.  ``mel(f) = 1127 ln(1 + f / 700)``; the
+    ``channels + 1`` centres are ``mel_lo + span / (channels + 1) (i + 1)``; ``hz_per_bin =
+    0.5 sample_rate / (bins - 1)``; bins ``start = int(1.5 + lower / hz_per_bin)`` to ``end =
+    int(upper / hz_per_bin)`` take part.  ``band[i]`` is the last centre (of the first
+    ``channels``) below the bin's mel, -1 below the first centre, and ``weight[i] = (centre[band
+    + 1] - mel_i) / (centre[band + 1] - centre[band])`` with ``mel_lo`` for ``centre[-1]``.
+    Raises ``ValueError`` when a channel receives no bin."""
+    import numpy as np
+
+    if bins < 2 or channels < 1 or sample_rate <= 0 or lower < 0 or upper <= lower:
+        raise ValueError(f"Mfcc: bins={bins}, channels={channels}, sample_rate={sample_rate}, "
+                         f"limits {lower}..{upper} are not a filter bank")
+
+    def mel(f):
+        return 1127.0 * math.log1p(f / 700.0)
+
+    mel_lo, mel_hi = mel(float(lower)), mel(float(upper))
+    spacing = (mel_hi - mel_lo) / (channels + 1)
+    centre = [mel_lo + spacing * (i + 1) for i in range(channels + 1)]
+    hz_per_bin = 0.5 * float(sample_rate) / (bins - 1)
+    start, end = int(1.5 + lower / hz_per_bin), min(int(upper / hz_per_bin), bins - 1)
+    band = np.full((bins,), -2, dtype=np.int64)
+    weight = np.zeros((bins,), dtype=np.float64)
+    ch = 0
+    for i in range(start, end + 1):
+        m = mel(i * hz_per_bin)
+        while ch < channels and centre[ch] < m:
+            ch += 1
+        band[i] = ch - 1
+        if ch - 1 >= 0:
+            weight[i] = (centre[ch] - m) / (centre[ch] - centre[ch - 1])
+        else:
+            weight[i] = (centre[0] - m) / (centre[0] - mel_lo)
+    hit = np.zeros((channels,), dtype=bool)
+    for i in range(start, end + 1):
+        if band[i] >= 0:
+            hit[band[i]] = True
+        if band[i] + 1 < channels:
+            hit[band[i] + 1] = True
+    if not hit.all():
+        raise ValueError(f"Mfcc: mel channels {np.nonzero(~hit)[0].tolist()} receive no spectrogram bin "
+                         f"({bins} bins, {sample_rate} Hz, {lower}..{upper} Hz, {channels} channels)")
+    return start, end, band, weight
+
+
+def mfcc(spectrogram, sample_rate, upper_frequency_limit=4000.0, lower_frequency_limit=20.0,
+         filterbank_channel_count=40, dct_coefficient_count=13):
+    """TF ``Mfcc``: squared-magnitude ``spectrogram [Ch, F, bins]`` to ``[Ch, F, D]`` float32.
+    With the filter bank of ``mel_filterbank`` and ``v = sqrt(spectrogram[i])``, taking the bins
+    in ascending order, channel ``band[i]`` gains ``v weight[i]`` (when ``band[i] >= 0``) and
+    channel ``band[i] + 1`` gains ``v - v weight[i]`` (when it is ``< C``); then ``log(max(.,
+    1e-12))``; then ``out[d] = sum_j sqrt(2 / C) cos(d pi / C (j + 0.5)) logmel[j]``.  ``D <= C``
+    is required.  Computed in float64."""
+    import numpy as np
+
+    if spectrogram.dim() != 3:
+        raise ValueError(f"Mfcc: spectrogram {tuple(spectrogram.shape)} is not [channels, frames, bins]")
+    C, D = int(filterbank_channel_count), int(dct_coefficient_count)
+    if D < 1 or D > C:
+        raise ValueError(f"Mfcc: dct_coefficient_count={D} must be in 1..filterbank_channel_count={C}")
+    Ch, F_, bins = spectrogram.shape
+    start, end, band, weight = mel_filterbank(bins, float(_scalar(sample_rate)), float(lower_frequency_limit),
+                                              float(upper_frequency_limit), C)
+    v = spectrogram.detach().to(torch.float64).cpu().numpy().reshape(Ch * F_, bins)
+    v = np.sqrt(v)
+    mel = np.zeros((Ch * F_, C), dtype=np.float64)
+    for i in range(start, end + 1):
+        c = int(band[i])
+        wv = v[:, i] * weight[i]
+        if c >= 0:
+            mel[:, c] += wv
+        if c + 1 < C:
+            mel[:, c + 1] += v[:, i] - wv
+    logmel = np.log(np.maximum(mel, 1e-12))
+    j = np.arange(C, dtype=np.float64)
+    dct = math.sqrt(2.0 / C) * np.cos(np.arange(D, dtype=np.float64)[:, None] * (math.pi / C) * (j[None, :] + 0.5))
+    out = logmel @ dct.T
+    return torch.from_numpy(out.astype(np.float32)).reshape(Ch, F_, D).to(spectrogram.device)
+
+
+def decode_wav(contents: bytes, desired_channels: int = -1, desired_samples: int = -1):
+    """TF ``DecodeWav``: RIFF / WAVE with 16-bit PCM only.  Returns ``(audio [samples, channels]
+    float32 = int16 / 32768, sample_rate)``; truncated or zero-padded to ``desired_samples``."""
+    import struct
+
+    import numpy as np
+
+    b = bytes(contents)
+    if len(b) < 12 or b[:4] != b"RIFF" or b[8:12] != b"WAVE":
+        raise ValueError("DecodeWav: not a RIFF/WAVE file")
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= len(b):
+        cid, size = b[pos:pos + 4], struct.unpack_from("<I", b, pos + 4)[0]
+        body = b[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            if size < 16 or len(body) < 16:
+                raise ValueError("DecodeWav: short fmt chunk")
+            fmt = struct.unpack_from("<HHIIHH", body, 0)
+        elif cid == b"data":
+            if len(body) != size:
+                raise ValueError("DecodeWav: data chunk runs past the end of the file")
+            data = body
+            break
+        pos += 8 + size + (size & 1)
+    if fmt is None or data is None:
+        raise ValueError("DecodeWav: missing fmt or data chunk")
+    tag, channels, rate, _, _, bits = fmt
+    if tag != 1 or bits != 16:
+        raise ValueError(f"DecodeWav: only 16-bit PCM is supported (format {tag}, {bits} bits)")
+    if channels < 1:
+        raise ValueError("DecodeWav: no channels")
+    if desired_channels not in (-1, channels):
+        raise ValueError(f"DecodeWav: the file has {channels} channels, desired_channels={desired_channels}")
+    pcm = np.frombuffer(data[:len(data) // (2 * channels) * 2 * channels], dtype="<i2").reshape(-1, channels)
+    if desired_samples >= 0:
+        if pcm.shape[0] >= desired_samples:
+            pcm = pcm[:desired_samples]
+        else:
+            pcm = np.concatenate([pcm, np.zeros((desired_samples - pcm.shape[0], channels), dtype=pcm.dtype)])
+    return torch.from_numpy(pcm.astype(np.float32) / np.float32(32768.0)), int(rate)
+
+
+@register("AudioSpectrogram")
+def _audio_spectrogram(ctx, node, x):
+    return (audio_spectrogram(x, int(node.attr("window_size")), int(node.attr("stride")),
+                              bool(node.attr("magnitude_squared", False))),)
+
+
+@register("Mfcc")
+def _mfcc(ctx, node, spectrogram, sample_rate):
+    return (mfcc(spectrogram, sample_rate, float(node.attr("upper_frequency_limit", 4000.0)),
+                 float(node.attr("lower_frequency_limit", 20.0)), int(node.attr("filterbank_channel_count", 40)),
+                 int(node.attr("dct_coefficient_count", 13))),)
+
+
+@register("DecodeWav")
+def _decode_wav(ctx, node, contents):
+    from ..types.tensor import StringTensor
+
+    if not isinstance(contents, StringTensor) or contents.numel() != 1:
+        raise TypeError("DecodeWav: contents is a scalar STRING tensor")
+    audio, rate = decode_wav(contents.array.reshape(-1)[0], int(node.attr("desired_channels", -1)),
+                             int(node.attr("desired_samples", -1)))
+    return audio.to(ctx.device), torch.tensor(rate, dtype=torch.int32, device=ctx.device)

@@ -31,6 +31,7 @@ void register_dwconv(pybind11::module_& m);
 void register_resize(pybind11::module_& m);
 void register_detection(pybind11::module_& m);
 void register_lstm(pybind11::module_& m);
+void register_audio(pybind11::module_& m);
 
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "flink_tensorflow_amd CDNA4 (gfx950) kernels";
@@ -57,6 +58,7 @@ PYBIND11_MODULE(_hip, m) {
   register_resize(m);
   register_detection(m);
   register_lstm(m);
+  register_audio(m);
   // Streams owned by the framework (not torch's round-robin pool of 32 per device): a pooled
   // stream handed to a runner can be the very stream another thread is capturing a hipGraph
   // on, and then that thread's launches land in the capture (or are rejected).

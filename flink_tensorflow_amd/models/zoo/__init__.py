@@ -2,7 +2,9 @@
 _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "mobilenet",
             "DeepLabV3Model": "image_classifier", "deeplab_v3_graph_def": "deeplab",
             "SSDMobileNetModel": "image_classifier", "ssd_mobilenet_v1_graph_def": "ssd",
-            "LSTMClassifierModel": "lstm", "lstm_classifier_graph_def": "lstm"}
+            "LSTMClassifierModel": "lstm", "lstm_classifier_graph_def": "lstm",
+            "KeywordSpotterModel": "speech", "speech_commands_graph_def": "speech",
+            "export_keyword_spotter_saved_model": "speech"}
 
 __all__ = sorted(_EXPORTS)
 

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import copy
 import functools
+import math
 import os
 
 import torch
@@ -1225,6 +1226,201 @@ def lstm_seq(xproj: torch.Tensor, wh_packed: torch.Tensor, h0: torch.Tensor, c0:
     if c_last is not None:
         c_last.copy_(c)
     return h_out
+
+
+# ------------------------------------------------------------------------------ audio front end
+AUDIO_FFT_LENGTHS = (256, 512, 1024, 2048)
+AUDIO_MAX_CHANNELS = 128
+AUDIO_FRAMES_PER_WG = 8  # frames one workgroup of kernels/audio.hip owns (four FFTs of two frames)
+_AUDIO_MODES = {"mfcc_f32": 0, "mfcc_bf16": 1, "mfcc_bf16_pad8": 2, "spec_squared": 3, "spec_magnitude": 4}
+
+
+def audio_fft_length(window_size: int) -> int:
+    """The smallest power of two ``>= window_size``."""
+    n = 1
+    while n < window_size:
+        n *= 2
+    return n
+
+
+def audio_frames(samples: int, window_size: int, stride: int) -> int:
+    return 1 + (samples - window_size) // stride if samples >= window_size else 0
+
+
+@functools.lru_cache(maxsize=64)
+def _audio_tables(window: int, sample_rate, lower, upper, C: int, D: int):
+    from ..graph.ops_nn import mel_filterbank
+
+    N = audio_fft_length(window)
+    n = torch.arange(window, dtype=torch.float64)
+    k = torch.arange(N // 2, dtype=torch.float64)
+    ang = 2.0 * math.pi * k / N
+    t = {"window": window, "fft": N, "C": C, "D": D,
+         "hann": (0.5 - 0.5 * torch.cos(2.0 * math.pi * n / window)).float(),
+         "twiddle": torch.stack([torch.cos(ang), -torch.sin(ang)], dim=1).float().contiguous()}
+    if C:
+        bins = N // 2 + 1
+        start, end, band, weight = mel_filterbank(bins, sample_rate, lower, upper, C)
+        chan = torch.zeros((C, 3), dtype=torch.int32)
+        for c in range(C):
+            prev = [i for i in range(start, end + 1) if band[i] == c - 1]  # they weigh in with 1 - w
+            own = [i for i in range(start, end + 1) if band[i] == c]
+            lo = prev[0] if prev else own[0]
+            mid = own[0] if own else prev[-1] + 1
+            chan[c] = torch.tensor([lo, mid, own[-1] + 1 if own else mid], dtype=torch.int32)
+        w = torch.from_numpy(weight)
+        j = torch.arange(C, dtype=torch.float64)
+        d = torch.arange(D, dtype=torch.float64)
+        t.update(chan=chan, wa=w.float(), wb=(1.0 - w).float(),
+                 dct=(math.sqrt(2.0 / C) * torch.cos(d[:, None] * (math.pi / C) * (j[None, :] + 0.5))).float().contiguous())
+    return t
+
+
+def mfcc_tables(window_size: int, sample_rate=None, lower: float = 20.0, upper: float = 4000.0, channels: int = 0,
+                dct_count: int = 0, device=None) -> dict:
+    """The fp32 tables of ``kernels/audio.hip``, computed in float64: ``hann [window]`` (periodic),
+    ``twiddle [N/2, 2]`` = ``(cos, -sin)(2 pi k / N)`` and, with ``channels > 0``, the mel filter
+    bank of ``graph.ops_nn.mel_filterbank`` per channel: ``chan [C, 3]`` int32 = ``(lo, mid, hi)``,
+    where bins ``[lo, mid)`` (those of the band below) weigh in with ``wb[i] = 1 - w_i`` and bins
+    ``[mid, hi)`` with ``wa[i] = w_i``; and ``dct [D, C]``.  ``ValueError`` when a channel receives
+    no bin or ``D > C``.  The CPU tables are cached; ``device`` moves a copy there."""
+    window_size, channels, dct_count = int(window_size), int(channels), int(dct_count)
+    if window_size < 2:
+        raise ValueError(f"mfcc_tables: window_size={window_size}")
+    if channels and not 1 <= dct_count <= channels:
+        raise ValueError(f"mfcc_tables: dct_count={dct_count} must be in 1..channels={channels}")
+    t = _audio_tables(window_size, None if not channels else float(sample_rate), float(lower), float(upper), channels,
+                      dct_count if channels else 0)
+    if device is None or torch.device(device).type == "cpu":
+        return t
+    return {k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in t.items()}
+
+
+def mfcc_eligible(samples: int, window_size: int, stride: int, channels: int = 0, dct_count: int = 0, sample_rate=None,
+                  lower: float = 20.0, upper: float = 4000.0) -> bool:
+    """What ``kernels/audio.hip`` takes: an FFT length of 256..2048 (``window_size`` 129..2048), any
+    ``stride >= 1``, at least one frame and, for the MFCC forms, ``D <= C <= 128`` with every mel
+    channel non-empty.  ``channels == 0`` asks for the spectrogram alone."""
+    if window_size < 2 or audio_fft_length(window_size) not in AUDIO_FFT_LENGTHS or stride < 1 \
+            or audio_frames(samples, window_size, stride) < 1:
+        return False
+    if not channels:
+        return True
+    if not (1 <= dct_count <= channels <= AUDIO_MAX_CHANNELS) or sample_rate is None or sample_rate <= 0:
+        return False
+    try:
+        mfcc_tables(window_size, sample_rate, lower, upper, channels, dct_count)
+    except ValueError:
+        return False
+    return True
+
+
+def _audio_args(name: str, x: torch.Tensor, tables: dict, stride: int, need_mfcc: bool):
+    if x.dim() != 2:
+        raise ValueError(f"{name}: x {tuple(x.shape)} is not [samples, clips]")
+    if x.dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"{name}: x is fp32 or int16, not {x.dtype}")
+    S, B = x.shape
+    window, N = tables["window"], tables["fft"]
+    if N not in AUDIO_FFT_LENGTHS or stride < 1:
+        raise ValueError(f"{name}: FFT length {N} (window {window}) / stride {stride} outside the kernel's envelope")
+    F_ = audio_frames(S, window, stride)
+    if F_ < 1 or B < 1:
+        raise ValueError(f"{name}: {S} samples hold no frame of {window}, or no clip")
+    if (S > 1 and x.stride(0) < 1) or (B > 1 and x.stride(1) < 1):
+        raise ValueError(f"{name}: x strides {x.stride()} must be positive")
+    names = ("hann", "twiddle") + (("chan", "wa", "wb", "dct") if need_mfcc else ())
+    if need_mfcc and not tables.get("C"):
+        raise ValueError(f"{name}: the tables hold no filter bank (mfcc_tables with channels > 0)")
+    shapes = {"hann": (window,), "twiddle": (N // 2, 2), "chan": (tables["C"], 3), "wa": (N // 2 + 1,),
+              "wb": (N // 2 + 1,), "dct": (tables["D"], tables["C"])}
+    for k in names:
+        t = tables[k]
+        _check(t, f"{name}: table {k}", torch.int32 if k == "chan" else torch.float32, x.device)
+        if tuple(t.shape) != shapes[k]:
+            raise ValueError(f"{name}: table {k} is {tuple(t.shape)}, not {shapes[k]}")
+    return S, B, F_, window, N
+
+
+def _audio_frames_host(x: torch.Tensor, tables: dict, stride: int, scale: float, F_: int) -> torch.Tensor:
+    """fp32 power spectrogram ``[B, F, bins]`` on the host path."""
+    window, N = tables["window"], tables["fft"]
+    xf = x.float() * scale if x.dtype == torch.int16 else x
+    fr = xf.t()[:, :(F_ - 1) * stride + window].unfold(1, window, stride) * tables["hann"]
+    z = torch.fft.rfft(fr.contiguous(), n=N, dim=-1)
+    return z.real * z.real + z.imag * z.imag
+
+
+def _launch_audio(x, tables, stride, scale, out, mode, S, B):
+    mf = mode.startswith("mfcc")
+    _hip().audio_frontend(x.data_ptr(), x.dtype == torch.int16, float(scale), max(x.stride(0), 1), max(x.stride(1), 1), S, B,
+                          tables["window"], int(stride), tables["fft"], tables["hann"].data_ptr(),
+                          tables["twiddle"].data_ptr(), tables["chan"].data_ptr() if mf else 0,
+                          tables["wa"].data_ptr() if mf else 0, tables["wb"].data_ptr() if mf else 0,
+                          tables["dct"].data_ptr() if mf else 0, tables["C"] if mf else 0, tables["D"] if mf else 0,
+                          out.data_ptr(), _AUDIO_MODES[mode], _stream())
+
+
+def audio_spectrogram(x: torch.Tensor, tables: dict, stride: int, magnitude_squared: bool = True, scale: float = 1.0,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """``AudioSpectrogram`` of ``B`` clips in one launch (``kernels/audio.hip``): ``x [S, B]`` fp32, or
+    int16 times ``scale``, read through its own strides (a ``[B, S]`` buffer goes in as ``buf.t()``),
+    to fp32 ``[B, F, N/2 + 1]``.  ``tables = mfcc_tables(window_size, device=x.device)``."""
+    S, B, F_, window, N = _audio_args("audio_spectrogram", x, tables, stride, False)
+    shape = (B, F_, N // 2 + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _check(out, "audio_spectrogram: out", torch.float32, x.device)
+    if tuple(out.shape) != shape:
+        raise ValueError(f"audio_spectrogram: out {tuple(out.shape)} is not {shape}")
+    if x.is_cuda:
+        _launch_audio(x, tables, stride, scale, out, "spec_squared" if magnitude_squared else "spec_magnitude", S, B)
+        return out
+    p = _audio_frames_host(x, tables, stride, scale, F_)
+    out.copy_(p if magnitude_squared else p.sqrt())
+    return out
+
+
+def audio_mfcc(x: torch.Tensor, tables: dict, stride: int, scale: float = 1.0, out: torch.Tensor | None = None,
+               out_dtype=torch.float32, pad8: bool = False) -> torch.Tensor:
+    """PCM to MFCC in one launch (``kernels/audio.hip``): ``AudioSpectrogram(magnitude_squared)``
+    followed by ``Mfcc``, with nothing in memory in between.  ``x [S, B]`` as for
+    ``audio_spectrogram``; ``tables = mfcc_tables(window_size, sample_rate, lower, upper, C, D,
+    device=x.device)``.  The result is ``[B, F, D]`` fp32 or bf16, or with ``pad8`` bf16 ``[B, F, D,
+    8]`` whose channel 0 holds the coefficients and channels 1..7 zeros (the padded input of a
+    convolution over ``[B, F, D, 1]``).  bf16 results are the fp32 ones rounded to nearest even."""
+    S, B, F_, window, N = _audio_args("audio_mfcc", x, tables, stride, True)
+    C, D = tables["C"], tables["D"]
+    if not 1 <= D <= C <= AUDIO_MAX_CHANNELS:
+        raise ValueError(f"audio_mfcc: D={D}, C={C} outside 1 <= D <= C <= {AUDIO_MAX_CHANNELS}")
+    if pad8:
+        out_dtype = torch.bfloat16
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"audio_mfcc: out_dtype is fp32 or bf16, not {out_dtype}")
+    shape = (B, F_, D, 8) if pad8 else (B, F_, D)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=x.device)
+    _check(out, "audio_mfcc: out", out_dtype, x.device)
+    if tuple(out.shape) != shape:
+        raise ValueError(f"audio_mfcc: out {tuple(out.shape)} is not {shape}")
+    if x.is_cuda:
+        if pad8 and out.data_ptr() % 16:
+            raise ValueError("audio_mfcc: the padded output must be 16-byte aligned")
+        mode = "mfcc_bf16_pad8" if pad8 else ("mfcc_f32" if out_dtype == torch.float32 else "mfcc_bf16")
+        _launch_audio(x, tables, stride, scale, out, mode, S, B)
+        return out
+    v = _audio_frames_host(x, tables, stride, scale, F_).sqrt()  # [B, F, bins]
+    bank = torch.zeros((N // 2 + 1, C), dtype=torch.float32)
+    for c, (lo, mid, hi) in enumerate(tables["chan"].tolist()):
+        bank[lo:mid, c] = tables["wb"][lo:mid]
+        bank[mid:hi, c] = tables["wa"][mid:hi]
+    res = torch.log((v @ bank).clamp_min(1e-12)) @ tables["dct"].t()
+    if pad8:
+        out.zero_()
+        out[..., 0] = res.to(torch.bfloat16)
+    else:
+        out.copy_(res.to(out_dtype))
+    return out
 
 
 # ------------------------------------------------------------------------------ pooling
