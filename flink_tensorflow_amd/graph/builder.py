@@ -131,6 +131,15 @@ class GraphBuilder:
         return self.op("Conv2D", [x, w], name=name, strides=[1, strides[0], strides[1], 1], padding=padding.encode(),
                        data_format=b"NHWC", dilations=[1, dilations[0], dilations[1], 1], use_cudnn_on_gpu=True)
 
+    def conv2d_transpose(self, x, w, output_hw, strides=(2, 2), padding="SAME", name=None) -> str:
+        """``Conv2DBackpropInput`` of ``x`` with ``w [KH, KW, Cout, Cin]`` to ``output_hw``.  The
+        ``input_sizes`` operand is TF's 2-vector ``[Ho, Wo]``, so the graph does not bake in its
+        batch."""
+        nm = name or "conv2d_transpose"
+        sizes = self.constant(f"{nm}/input_sizes", np.asarray(output_hw, dtype=np.int32))
+        return self.op("Conv2DBackpropInput", [sizes, w, x], name=nm, strides=[1, strides[0], strides[1], 1],
+                       padding=padding.encode(), data_format=b"NHWC", dilations=[1, 1, 1, 1], use_cudnn_on_gpu=True)
+
     def fused_batch_norm(self, x, scale, offset, mean, var, epsilon=1e-3, name=None) -> str:
         return self.op("FusedBatchNormV3", [x, scale, offset, mean, var], name=name, epsilon=float(epsilon),
                        is_training=False, data_format=b"NHWC")

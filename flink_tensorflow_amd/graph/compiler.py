@@ -15,6 +15,9 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``DepthwiseConv2dNative → [BiasAdd | FusedBatchNorm]* → [Relu|Relu6]`` → one launch of
      the depthwise kernel (3x3 register-tiled or generic), BN folded into the per-channel
      filter; a residual ``Add`` behind it stays an elementwise step;
+   * ``Conv2DBackpropInput → [BiasAdd | FusedBatchNorm]* → [Relu|Relu6]`` → one launch of the
+     transposed-conv kernel (kernels/deconv.hip, ``deconv_lowering.py``), one implicit GEMM per
+     output phase; stride 1 runs as a plain conv with the flipped filter;
    * ``ResizeBilinear`` of an activation → the bilinear resize kernel (it writes concat
      slots); ``[ResizeBilinear] → ArgMax(channels) → [Cast]`` → one fused resize + ArgMax
      launch that never stores the resized tensor (kernels/resize.hip);
@@ -40,13 +43,14 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is nine modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+The compiler is ten modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
 map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
 pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
 ``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
 mixin: box decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering`` mixin: ``BlockLSTM`` and the layout
 ops around it), ``audio_lowering.py`` (the ``AudioLowering`` mixin: the spectrogram / MFCC front end and the
-ops it absorbs), ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
+ops it absorbs), ``deconv_lowering.py`` (the ``DeconvLowering`` mixin: ``Conv2DBackpropInput`` chains),
+``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
 ``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
 bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
 
@@ -78,6 +82,7 @@ from ..utils import tracing
 from . import ops_core  # noqa: F401
 from .audio_lowering import AudioLowering
 from .conv_lowering import _ACTS, ConvLowering
+from .deconv_lowering import DeconvLowering
 from .detection_lowering import _UNPADDED_NMS, DetectionLowering
 from .graph import Graph, Node
 from .op_registry import OpContext, lookup
@@ -108,7 +113,8 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering, ConvLowering, PlanMemory, PlanRunner):
+class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering, DeconvLowering, ConvLowering,
+                       PlanMemory, PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -400,6 +406,8 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
             return self._lower_conv(node)
         if op == "DepthwiseConv2dNative":
             return self._lower_dwconv(node)
+        if op == "Conv2DBackpropInput":
+            return self._lower_deconv(node)
         if op == "MatMul":
             return self._lower_matmul(node)
         if op == "Cast" and self._try_preprocess(node):
@@ -921,10 +929,10 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self.vals[(node.name, 0)] = out
 
     def _concat_writable(self, v: Val, src_node: str, concat_node: str) -> bool:
-        # produced by exactly one conv/pool/resize step (which can write at a channel offset),
+        # produced by exactly one conv/pool/resize/deconv step (which can write at a channel offset),
         # consumed by nothing but this concat, and not fetched
         prods = [s for s in self.steps if any(o is v for o in s.outputs)]
-        if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize") \
+        if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize", "deconv") \
                 or v.concat_slot is not None \
                 or (len(prods[0].outputs) != 1 and not prods[0].meta.get("multi_out")):
             return False
@@ -938,7 +946,10 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
             return v.shape[-1] % 16 == 0 and src_node in self.cons
         return v.shape[-1] % 8 == 0 and v.dtype == torch.bfloat16 and src_node in self.cons
 
-    def _lower_glue(self, node: Node):
+    def _lower_glue(self, node: Node, host_consts=()):
+        """``node`` as a captured interpreter op.  ``host_consts``: the inputs whose constants stay on
+        the host (a shape operand the op reads into Python ints, which a capture does not allow of a
+        device tensor)."""
         if any(self.vals.get(s) is not None and self.vals[s].rows is not None for s in node.inputs):
             raise CompileError(f"{node.op} {node.name} reads token-packed rows; no packed lowering")
         if self.strict:
@@ -955,8 +966,9 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
                                                           else v.dtype) for v in ins]
         outs = fn(ctx, node, *probe)
         outv = [self._new(o.shape, torch.bfloat16 if o.dtype == torch.float32 else o.dtype) for o in outs]
-        dev_consts = [None if not v.is_const else (v.const.to(self.device) if isinstance(v.const, torch.Tensor)
-                                                    else v.const) for v in ins]
+        dev_consts = [None if not v.is_const else
+                      (v.const.to(self.device) if isinstance(v.const, torch.Tensor) and i not in host_consts else v.const)
+                      for i, v in enumerate(ins)]
         dctx = OpContext(self._const_sess, self.device)
 
         def run(node=node, ins=ins, outv=outv, dev_consts=dev_consts):

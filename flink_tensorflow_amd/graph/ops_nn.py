@@ -85,6 +85,67 @@ def _conv2d(ctx, node, x, w):
     return (y,)
 
 
+def conv2d_transpose_tf(x, w, out_hw, strides=(2, 2), padding="SAME", dilations=(1, 1), explicit=((0, 0), (0, 0))):
+    """NHWC transposed conv (``Conv2DBackpropInput``): ``x`` is ``[N, Hi, Wi, Cin]``, ``w`` is
+    ``[KH, KW, Cout, Cin]``, the result ``[N, Ho, Wo, Cout]`` with ``(Ho, Wo) = out_hw``::
+
+        y[n, oy, ox, co] = sum x[n, iy, ix, ci] * w[ky, kx, co, ci]
+
+    over the taps with ``oy + pt - ky == iy * sh``, ``0 <= iy < Hi``, and likewise in x;
+    ``pt = same_pads(Ho, KH, sh)[0]`` for ``SAME`` and ``0`` for ``VALID``.  Output rows that no
+    tap reaches are zero.  Arithmetic is float64 or the input dtype, like ``conv2d_tf``.  An
+    ``out_hw`` whose forward conv would not produce ``[Hi, Wi]`` is rejected, as TF does.
+    With ``dilations`` the tap offset is ``ky * dh``; ``padding="EXPLICIT"`` takes ``pt`` from
+    ``explicit = ((top, bottom), (left, right))`` (interpreter only: neither is lowered)."""
+    sh, sw = strides
+    KH, KW, Cout, Cin = w.shape
+    N, Hi, Wi, C = x.shape
+    Ho, Wo = (int(v) for v in out_hw)
+    if C != Cin:
+        raise ValueError(f"conv2d_transpose: input has {C} channels, the filter expects {Cin}")
+    dh, dw = dilations
+    if padding not in ("SAME", "VALID", "EXPLICIT"):
+        raise ValueError(f"conv2d_transpose: padding {padding!r} is not SAME, VALID or EXPLICIT")
+    fwd = (conv_out_size(Ho, KH, sh, padding, dh, explicit[0]), conv_out_size(Wo, KW, sw, padding, dw, explicit[1]))
+    if Ho < 1 or Wo < 1 or fwd != (Hi, Wi):
+        raise ValueError(f"conv2d_transpose: a {KH}x{KW}/{sh}x{sw} {padding} conv of [{Ho}, {Wo}] does not give "
+                         f"[{Hi}, {Wi}]")
+    if padding == "SAME":
+        pt, pl = same_pads(Ho, KH, sh, dh)[0], same_pads(Wo, KW, sw, dw)[0]
+    else:
+        pt, pl = (explicit[0][0], explicit[1][0]) if padding == "EXPLICIT" else (0, 0)
+    # the scatter form: input pixel iy adds to rows iy * sh + ky - pt; then the window [pt, pt + Ho)
+    full = F.conv_transpose2d(x.permute(0, 3, 1, 2), w.permute(3, 2, 0, 1).to(x.dtype), stride=(sh, sw),
+                              dilation=(dh, dw))
+    full = full[:, :, pt:pt + Ho, pl:pl + Wo]
+    if full.shape[2] != Ho or full.shape[3] != Wo:  # VALID with extra rows: no tap reaches them
+        full = F.pad(full, (0, Wo - full.shape[3], 0, Ho - full.shape[2]))
+    return full.permute(0, 2, 3, 1).contiguous()
+
+
+@register("Conv2DBackpropInput")
+def _conv2d_backprop_input(ctx, node, input_sizes, w, x):
+    fmt = node.attr("data_format", "NHWC")
+    pad = node.attr("padding", "SAME")
+    sizes = [int(v) for v in torch.as_tensor(input_sizes).reshape(-1).tolist()]
+    if len(sizes) == 4:
+        out_hw = (sizes[1], sizes[2]) if fmt == "NHWC" else (sizes[2], sizes[3])
+    elif len(sizes) == 2:
+        out_hw = tuple(sizes)
+    else:
+        raise ValueError(f"Conv2DBackpropInput {node.name}: input_sizes must have 2 or 4 elements")
+    if fmt == "NCHW":
+        x = x.permute(0, 2, 3, 1)
+    # TF's filter is [KH, KW, in, out] of the forward conv: ``in`` is this op's output channels
+    y = conv2d_transpose_tf(x, w, out_hw, _hw(node.attr("strides"), fmt), pad, _hw(node.attr("dilations"), fmt),
+                            _explicit_pads(node, fmt))
+    if len(sizes) == 4 and (sizes[0], sizes[3 if fmt == "NHWC" else 1]) != (y.shape[0], y.shape[3]):
+        raise ValueError(f"Conv2DBackpropInput {node.name}: input_sizes {sizes} != result {tuple(y.shape)}")
+    if fmt == "NCHW":
+        y = y.permute(0, 3, 1, 2).contiguous()
+    return (y,)
+
+
 @register("DepthwiseConv2dNative")
 def _dwconv(ctx, node, x, w):
     fmt = node.attr("data_format", "NHWC")

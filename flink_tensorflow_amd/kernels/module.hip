@@ -32,6 +32,7 @@ void register_resize(pybind11::module_& m);
 void register_detection(pybind11::module_& m);
 void register_lstm(pybind11::module_& m);
 void register_audio(pybind11::module_& m);
+void register_deconv(pybind11::module_& m);
 
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "flink_tensorflow_amd CDNA4 (gfx950) kernels";
@@ -59,6 +60,7 @@ PYBIND11_MODULE(_hip, m) {
   register_detection(m);
   register_lstm(m);
   register_audio(m);
+  register_deconv(m);
   // Streams owned by the framework (not torch's round-robin pool of 32 per device): a pooled
   // stream handed to a runner can be the very stream another thread is capturing a hipGraph
   // on, and then that thread's launches land in the capture (or are rejected).

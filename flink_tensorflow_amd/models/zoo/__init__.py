@@ -1,6 +1,7 @@
 """Model zoo.  The model classes load lazily: importing the package pulls in no compiler."""
 _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "mobilenet",
             "DeepLabV3Model": "image_classifier", "deeplab_v3_graph_def": "deeplab",
+            "UNetModel": "image_classifier", "unet_graph_def": "unet", "export_unet_saved_model": "unet",
             "SSDMobileNetModel": "image_classifier", "ssd_mobilenet_v1_graph_def": "ssd",
             "LSTMClassifierModel": "lstm", "lstm_classifier_graph_def": "lstm",
             "KeywordSpotterModel": "speech", "speech_commands_graph_def": "speech",

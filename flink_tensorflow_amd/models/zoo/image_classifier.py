@@ -274,6 +274,29 @@ class DeepLabV3Model(ImageClassifierModel):
         return list(br.outputs[0][: br.n].numpy()), br.tags, br.latencies
 
 
+class UNetModel(DeepLabV3Model):
+    """U-Net (random-init frozen graph): the image-to-image family.  The plan is strict: the
+    encoder and decoder convs on the conv kernels, every ``Conv2DBackpropInput`` up-conv with its
+    bias as one launch of the transposed-conv kernel (``kernels/deconv.hip``), the ArgMax storing
+    the uint8 label map.  Results are ``[H, W]`` uint8 maps at ``crop_hw``, one per image, from
+    ``segment`` and from the batched ``submit`` / ``poll`` / ``drain`` path alike."""
+
+    def __init__(self, image_hw=(256, 256), buckets=(8, 32), seed: int = 0, device=None, base: int = 64,
+                 depth: int = 4, crop_hw=(256, 256), num_classes: int = 21, fetches=("label_map:0",), **kw):
+        self.seed = seed
+        self.base_channels = base
+        self.levels = depth  # (``depth`` is the base class's queue depth)
+        self.crop_hw = tuple(crop_hw)
+        self.num_classes = num_classes
+        ImageClassifierModel.__init__(self, self._make_graph, image_hw, buckets, 1, device=device, fetches=fetches, **kw)
+
+    def _make_graph(self) -> GraphDef:
+        from .unet import unet_graph_def
+
+        return unet_graph_def(base=self.base_channels, depth=self.levels, num_classes=self.num_classes, image_hw=self.image_hw,
+                              crop_hw=self.crop_hw, seed=self.seed)
+
+
 class SSDMobileNetModel(ImageClassifierModel):
     """SSD-MobileNet-V1 (random-init frozen graph): object detection.  The plan is strict: the
     MobileNet-V1 backbone on the depthwise kernel and the implicit GEMM, the box and class

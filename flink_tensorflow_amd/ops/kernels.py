@@ -874,6 +874,136 @@ def dwconv2d_nhwc(x: torch.Tensor, w_taps_c: torch.Tensor, bias: torch.Tensor | 
     return out
 
 
+# ------------------------------------------------------------------------------ transposed conv
+# tile configurations of ``deconv_nhwc_bf16`` (kernels/deconv.hip); -1 = the launcher's choice
+DECONV_TILES = {"128x128": 0, "256x64": 1}
+
+
+def deconv_eligible(Cin: int, Cout: int, KH: int, KW: int, stride=(2, 2)) -> bool:
+    """What ``deconv_nhwc_bf16`` takes: 8-channel vectors on both sides, a filter of at most
+    8x8, strides 1..4 per axis."""
+    return (Cin > 0 and Cin % 8 == 0 and Cout > 0 and Cout % 8 == 0 and 1 <= KH <= 8 and 1 <= KW <= 8
+            and len(stride) == 2 and all(1 <= s <= 4 for s in stride))
+
+
+def _deconv_pads(pad) -> tuple[int, int]:
+    """(top, left) of ``pad = (top, bottom, left, right)`` or ``(top, left)``; the far sides are
+    implied by the output size."""
+    return (int(pad[0]), int(pad[2])) if len(pad) == 4 else (int(pad[0]), int(pad[1]))
+
+
+def deconv_phases(kernel, stride, pad, Cin: int = 1, Cout: int = 1) -> list[dict]:
+    """The per-phase table of a transposed conv, in packing order (``py * sw + px``): ``taps`` is
+    the list of ``(ky, kx, dy, dx)`` with ``ky = (py + pt) mod sh`` and ``kx = (px + pl) mod sw``, in
+    (ky, kx) order, read at input pixel ``(qy + dy, qx + dx)``; ``k`` the K extent ``len(taps) * Cin``; ``offset`` the
+    element offset of the phase's ``[Cout, k]`` matrix in the packed tensor."""
+    (KH, KW), (sh, sw), (pt, pl) = kernel, stride, _deconv_pads(pad)
+    out, off = [], 0
+    for py in range(sh):
+        for px in range(sw):
+            taps = [(ky, kx, (py + pt - ky) // sh, (px + pl - kx) // sw)
+                    for ky in range(KH) if (py + pt - ky) % sh == 0
+                    for kx in range(KW) if (px + pl - kx) % sw == 0]
+            out.append({"py": py, "px": px, "taps": taps, "k": len(taps) * Cin, "offset": off})
+            off += len(taps) * Cin * Cout
+    return out
+
+
+def deconv_pack_weights(w: torch.Tensor, stride, pad) -> torch.Tensor:
+    """TF's ``[KH, KW, Cout, Cin]`` filter as the flat tensor the kernel reads: phase-major, per
+    phase ``[Cout, taps * Cin]`` with K-contiguous rows (``deconv_phases``).  Same dtype and
+    device as ``w``; ``KH * KW * Cout * Cin`` elements, since every tap is in exactly one phase."""
+    KH, KW, Cout, Cin = w.shape
+    parts = []
+    for ph in deconv_phases((KH, KW), stride, pad, Cin, Cout):
+        if ph["taps"]:
+            parts.append(torch.stack([w[ky, kx] for ky, kx, _, _ in ph["taps"]], dim=1).reshape(-1))
+    return torch.cat(parts).contiguous()
+
+
+def deconv_unpack_weights(w_packed: torch.Tensor, kernel, stride, pad, Cin: int, Cout: int) -> torch.Tensor:
+    """Inverse of ``deconv_pack_weights``: the ``[KH, KW, Cout, Cin]`` filter."""
+    KH, KW = kernel
+    w = torch.zeros((KH, KW, Cout, Cin), dtype=w_packed.dtype, device=w_packed.device)
+    for ph in deconv_phases(kernel, stride, pad, Cin, Cout):
+        m = w_packed[ph["offset"]:ph["offset"] + Cout * ph["k"]].reshape(Cout, len(ph["taps"]), Cin)
+        for t, (ky, kx, _, _) in enumerate(ph["taps"]):
+            w[ky, kx] = m[:, t]
+    return w
+
+
+def deconv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, out_hw, kernel, stride=(2, 2),
+                  pad=(0, 0, 0, 0), act=None, out: torch.Tensor | None = None, out_channel_offset: int = 0,
+                  cfg: int = -1) -> torch.Tensor:
+    """Transposed NHWC conv ``act(deconv(x, w) + bias)`` to ``out_hw = (Ho, Wo)``:
+    ``y[n, oy, ox, co] = sum x[n, iy, ix, ci] w[ky, kx, co, ci]`` over ``oy + pt - ky == iy * sh``.
+
+    ``w_packed`` comes from ``deconv_pack_weights`` (its length gives ``Cout``); ``pad`` is
+    ``(top, bottom, left, right)`` of the forward conv, of which top and left are used.  With
+    ``out`` given, the result is written at channel offset ``out_channel_offset`` of it.
+    ``cfg`` pins a tile configuration (``DECONV_TILES``): measurement and tests only."""
+    a = act_code(act)
+    if a not in (ACT_NONE, ACT_RELU, ACT_RELU6):
+        raise ValueError("deconv2d_nhwc: act must be none, relu or relu6")
+    if x.dim() != 4 or w_packed.dim() != 1:
+        raise ValueError("deconv2d_nhwc: x must be [N, Hi, Wi, Cin] and w_packed flat")
+    N, Hi, Wi, Cin = x.shape
+    (KH, KW), (sh, sw), (Ho, Wo) = (int(v) for v in kernel), (int(v) for v in stride), (int(v) for v in out_hw)
+    pt, pl = _deconv_pads(pad)
+    taps = KH * KW
+    if min(N, Hi, Wi, Cin, taps) < 1 or w_packed.numel() % (taps * Cin) or w_packed.numel() == 0:
+        raise ValueError(f"deconv2d_nhwc: {w_packed.numel()} packed weights do not match a {KH}x{KW} filter over "
+                         f"{Cin} input channels")
+    Cout = w_packed.numel() // (taps * Cin)
+    if not deconv_eligible(Cin, Cout, KH, KW, (sh, sw)) or not (0 <= pt < KH and 0 <= pl < KW):
+        raise ValueError(f"deconv2d_nhwc: unsupported Cin={Cin}, Cout={Cout}, {KH}x{KW}, stride {(sh, sw)}, "
+                         f"pad {(pt, pl)}")
+    if Ho < 1 or Wo < 1:
+        raise ValueError("deconv2d_nhwc: empty output")
+    if cfg not in (-1, *DECONV_TILES.values()):
+        raise ValueError(f"deconv2d_nhwc: unknown tile configuration {cfg}")
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cout), dtype=x.dtype if x.is_cuda else torch.float32, device=x.device)
+        out_channel_offset = 0
+    if out.dim() != 4 or out.shape[:3] != (N, Ho, Wo) or out_channel_offset < 0 \
+            or out_channel_offset + Cout > out.shape[3]:
+        raise ValueError(f"deconv2d_nhwc: out {tuple(out.shape)} cannot hold [{N},{Ho},{Wo},{Cout}] at "
+                         f"offset {out_channel_offset}")
+    if bias is not None and bias.numel() != Cout:
+        raise ValueError("deconv2d_nhwc: bias must have Cout elements")
+    if x.is_cuda:
+        for t, n in ((x, "x"), (w_packed, "w_packed"), (out, "out")):
+            _check(t, n, device=x.device)
+        if bias is not None:
+            _check(bias, "bias", torch.float32, x.device)
+        else:
+            bias = _zeros_bias(Cout, x.device)
+        if out.shape[3] % 8 or out_channel_offset % 8:
+            raise ValueError("deconv2d_nhwc: output row pitch and channel offset must be multiples of 8")
+        _hip().deconv_nhwc_bf16(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), N, Hi, Wi, Cin,
+                                Ho, Wo, Cout, KH, KW, sh, sw, pt, pl, a, out.shape[3], out_channel_offset,
+                                w_packed.numel(), cfg, _stream())
+        return out
+    # host reference, phase by phase from the packed layout, as the kernel walks it
+    xf = x.float()
+    y = torch.zeros((N, Ho, Wo, Cout), dtype=torch.float32)
+    for ph in deconv_phases((KH, KW), (sh, sw), (pt, pl), Cin, Cout):
+        sub = y[:, ph["py"]::sh, ph["px"]::sw]
+        Hq, Wq = sub.shape[1:3]
+        m = w_packed[ph["offset"]:ph["offset"] + Cout * ph["k"]].float().reshape(Cout, len(ph["taps"]), Cin)
+        for t, (_, _, dy, dx) in enumerate(ph["taps"]):
+            # output (qy, qx) of the phase reads input (qy + dy, qx + dx) where that is inside x
+            q0, q1 = max(0, -dy), min(Hq, Hi - dy)
+            r0, r1 = max(0, -dx), min(Wq, Wi - dx)
+            if q0 < q1 and r0 < r1:
+                sub[:, q0:q1, r0:r1] += xf[:, q0 + dy:q1 + dy, r0 + dx:r1 + dx] @ m[:, t].t()
+    if bias is not None:
+        y = y + bias.float()
+    y = _apply_act_ref(y, a)
+    out[..., out_channel_offset:out_channel_offset + Cout] = y.to(out.dtype)
+    return out
+
+
 # ------------------------------------------------------------------------------ bilinear resize / ArgMax
 # kernel of ``resize_argmax_nhwc`` (kernels/resize.hip); 0 = the launcher's choice
 RESIZE_ARGMAX_PATHS = {"staged": 1, "simple": -1}
