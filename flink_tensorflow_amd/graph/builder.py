@@ -140,6 +140,19 @@ class GraphBuilder:
         return self.op("Conv2DBackpropInput", [sizes, w, x], name=nm, strides=[1, strides[0], strides[1], 1],
                        padding=padding.encode(), data_format=b"NHWC", dilations=[1, 1, 1, 1], use_cudnn_on_gpu=True)
 
+    def conv3d(self, x, w, strides=(1, 1, 1), padding="SAME", name=None, dilations=(1, 1, 1)) -> str:
+        """``Conv3D`` of NDHWC ``x`` with ``w [KD, KH, KW, Cin, Cout]``."""
+        return self.op("Conv3D", [x, w], name=name, strides=[1, *strides, 1], padding=padding.encode(),
+                       data_format=b"NDHWC", dilations=[1, *dilations, 1])
+
+    def max_pool3d(self, x, ksize, strides, padding="VALID", name=None) -> str:
+        return self.op("MaxPool3D", [x], name=name, ksize=[1, *ksize, 1], strides=[1, *strides, 1],
+                       padding=padding.encode(), data_format=b"NDHWC")
+
+    def avg_pool3d(self, x, ksize, strides, padding="VALID", name=None) -> str:
+        return self.op("AvgPool3D", [x], name=name, ksize=[1, *ksize, 1], strides=[1, *strides, 1],
+                       padding=padding.encode(), data_format=b"NDHWC")
+
     def fused_batch_norm(self, x, scale, offset, mean, var, epsilon=1e-3, name=None) -> str:
         return self.op("FusedBatchNormV3", [x, scale, offset, mean, var], name=name, epsilon=float(epsilon),
                        is_training=False, data_format=b"NHWC")

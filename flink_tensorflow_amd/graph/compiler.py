@@ -18,6 +18,10 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``Conv2DBackpropInput → [BiasAdd | FusedBatchNorm]* → [Relu|Relu6]`` → one launch of the
      transposed-conv kernel (kernels/deconv.hip, ``deconv_lowering.py``), one implicit GEMM per
      output phase; stride 1 runs as a plain conv with the flipped filter;
+   * ``Conv3D → [BiasAdd | FusedBatchNorm]* → [Relu|Relu6]`` → one launch of the 3-D implicit-GEMM
+     kernel (kernels/conv3d.hip, ``conv3d_lowering.py``); a conv that is 2-D over the same memory
+     (``KD == 1``, or ``KH == KW == 1``) runs on the 2-D kernels; ``MaxPool3D`` / ``AvgPool3D`` → the
+     3-D pool kernel; a uint8 clip feed's ``Cast → Mul`` folds into the first conv;
    * ``ResizeBilinear`` of an activation → the bilinear resize kernel (it writes concat
      slots); ``[ResizeBilinear] → ArgMax(channels) → [Cast]`` → one fused resize + ArgMax
      launch that never stores the resized tensor (kernels/resize.hip);
@@ -43,13 +47,14 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is ten modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+The compiler is eleven modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
 map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
 pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
 ``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
 mixin: box decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering`` mixin: ``BlockLSTM`` and the layout
 ops around it), ``audio_lowering.py`` (the ``AudioLowering`` mixin: the spectrogram / MFCC front end and the
 ops it absorbs), ``deconv_lowering.py`` (the ``DeconvLowering`` mixin: ``Conv2DBackpropInput`` chains),
+``conv3d_lowering.py`` (the ``Conv3DLowering`` mixin: ``Conv3D`` chains, 3-D pools, uint8 clips),
 ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
 ``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
 bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
@@ -81,6 +86,7 @@ from ..types.names import TensorName
 from ..utils import tracing
 from . import ops_core  # noqa: F401
 from .audio_lowering import AudioLowering
+from .conv3d_lowering import Conv3DLowering
 from .conv_lowering import _ACTS, ConvLowering
 from .deconv_lowering import DeconvLowering
 from .detection_lowering import _UNPADDED_NMS, DetectionLowering
@@ -113,8 +119,8 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering, DeconvLowering, ConvLowering,
-                       PlanMemory, PlanRunner):
+class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering, DeconvLowering,
+                       Conv3DLowering, ConvLowering, PlanMemory, PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -408,9 +414,15 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
             return self._lower_dwconv(node)
         if op == "Conv2DBackpropInput":
             return self._lower_deconv(node)
+        if op == "Conv3D":
+            return self._lower_conv3d(node)
+        if op in ("MaxPool3D", "AvgPool3D"):
+            return self._lower_pool3d(node)
         if op == "MatMul":
             return self._lower_matmul(node)
         if op == "Cast" and self._try_preprocess(node):
+            return
+        if op == "Cast" and self._lower_clip_cast(node):
             return
         if op == "ResizeBilinear":
             return self._lower_resize(node)
@@ -429,7 +441,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         if op in ("MaxPool", "AvgPool"):
             return self._lower_pool(node)
         if op == "Mean":
-            if self._lower_mean(node):
+            if self._lower_mean(node) or self._lower_mean3d(node):
                 return
         if op == "Softmax":
             return self._lower_softmax(node)
@@ -907,7 +919,7 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
             out.qscale = self._qscale(node.name)
         # one storage format per buffer: all fp8 at the concat's scale, or all bf16 (an fp8
         # plan's resize or depthwise branch next to fp8 convs is joined by the bf16 copy below)
-        stride_write = (axis == len(shape) - 1 and len(shape) == 4
+        stride_write = (axis == len(shape) - 1 and len(shape) in (4, 5)
                         and (fp8 or not any(v.qscale is not None for v in ins))
                         and all(self._concat_writable(v, node.inputs[i][0], node.name) for i, v in enumerate(ins)))
         if stride_write:
@@ -929,10 +941,11 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self.vals[(node.name, 0)] = out
 
     def _concat_writable(self, v: Val, src_node: str, concat_node: str) -> bool:
-        # produced by exactly one conv/pool/resize/deconv step (which can write at a channel offset),
+        # produced by exactly one conv/pool/resize/deconv/conv3d/pool3d step (which can write at a channel offset),
         # consumed by nothing but this concat, and not fetched
         prods = [s for s in self.steps if any(o is v for o in s.outputs)]
-        if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize", "deconv") \
+        if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize", "deconv",
+                                                        "conv3d", "pool3d") \
                 or v.concat_slot is not None \
                 or (len(prods[0].outputs) != 1 and not prods[0].meta.get("multi_out")):
             return False

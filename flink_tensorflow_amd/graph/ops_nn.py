@@ -146,6 +146,112 @@ def _conv2d_backprop_input(ctx, node, input_sizes, w, x):
     return (y,)
 
 
+def _dhw(attr, fmt, name):
+    """The (depth, height, width) entries of a 5-vector attribute; TF rejects a batch or channel
+    entry other than 1."""
+    a = [1] * 5 if attr is None else [int(v) for v in attr]
+    if len(a) != 5:
+        raise ValueError(f"{name} must have 5 entries, got {a}")
+    n, c = (0, 4) if fmt == "NDHWC" else (0, 1)
+    if a[n] != 1 or a[c] != 1:
+        raise ValueError(f"{name} {a}: the batch and channel entries must be 1")
+    return tuple(a[1:4]) if fmt == "NDHWC" else tuple(a[2:5])
+
+
+def conv3d_tf(x, w, strides=(1, 1, 1), padding="SAME", dilations=(1, 1, 1)):
+    """NDHWC 3-D conv (``Conv3D``): ``x`` is ``[N, D, H, W, Cin]``, ``w`` is ``[KD, KH, KW, Cin,
+    Cout]``, the result ``[N, Do, Ho, Wo, Cout]``::
+
+        y[n, od, oh, ow, co] = sum x[n, od sd + kd dd - pf, oh sh + kh dh - pt, ow sw + kw dw - pl, ci]
+                                   * w[kd, kh, kw, ci, co]
+
+    over the taps whose input index is inside ``x`` on all three axes.  Per axis ``SAME`` gives
+    ``out = ceil(in / s)`` and the front pad ``same_pads(in, k, s, d)[0]`` (the extra element goes
+    behind); ``VALID`` gives ``out = (in - (k - 1) d - 1) // s + 1`` and no pad.  Arithmetic is
+    float64 or the input dtype, like ``conv2d_tf``.  A channel mismatch and an empty output are
+    rejected, as TF does."""
+    if x.dim() != 5 or w.dim() != 5:
+        raise ValueError(f"conv3d: input {tuple(x.shape)} / filter {tuple(w.shape)} are not 5-D")
+    KD, KH, KW, Cin, Cout = w.shape
+    N, D, H, W, C = x.shape
+    if C != Cin:
+        raise ValueError(f"conv3d: input has {C} channels, the filter expects {Cin}")
+    if padding not in ("SAME", "VALID"):
+        raise ValueError(f"conv3d: padding {padding!r} is not SAME or VALID")
+    ext, ks = (D, H, W), (KD, KH, KW)
+    pads = [same_pads(i, k, s, d) if padding == "SAME" else (0, 0) for i, k, s, d in zip(ext, ks, strides, dilations)]
+    outs = [conv_out_size(i, k, s, padding, d) for i, k, s, d in zip(ext, ks, strides, dilations)]
+    if min(outs) < 1:
+        raise ValueError(f"conv3d: a {KD}x{KH}x{KW} {padding} conv of {ext} has an empty output {tuple(outs)}")
+    xn = x.permute(0, 4, 1, 2, 3)
+    if any(any(p) for p in pads):
+        xn = F.pad(xn, (*pads[2], *pads[1], *pads[0]))
+    y = F.conv3d(xn, w.permute(4, 3, 0, 1, 2).to(xn.dtype), stride=tuple(strides), dilation=tuple(dilations))
+    return y.permute(0, 2, 3, 4, 1).contiguous()
+
+
+@register("Conv3D")
+def _conv3d(ctx, node, x, w):
+    fmt = node.attr("data_format", "NDHWC")
+    s = _dhw(node.attr("strides"), fmt, f"Conv3D {node.name}: strides")
+    d = _dhw(node.attr("dilations"), fmt, f"Conv3D {node.name}: dilations")
+    if fmt == "NCDHW":
+        x = x.permute(0, 2, 3, 4, 1)
+    y = conv3d_tf(x, w, s, node.attr("padding", "SAME"), d)
+    if fmt == "NCDHW":
+        y = y.permute(0, 4, 1, 2, 3).contiguous()
+    return (y,)
+
+
+def pool3d_tf(x, ksize, strides, padding, mode):
+    """NDHWC 3-D pooling (``MaxPool3D`` / ``AvgPool3D``) with windows ``ksize = (kd, kh, kw)``::
+
+        y[n, od, oh, ow, c] = max | mean of x[n, od sd + i - pf, oh sh + j - pt, ow sw + k - pl, c]
+
+    over the window elements inside ``x``; output sizes and pads per axis as ``conv3d_tf``.
+    Padding never wins a max, and a mean divides by the number of elements inside the input
+    (TF's rule, and ``pool_tf``'s)."""
+    if x.dim() != 5:
+        raise ValueError(f"pool3d: input {tuple(x.shape)} is not 5-D")
+    if padding not in ("SAME", "VALID") or mode not in ("max", "avg"):
+        raise ValueError(f"pool3d: padding {padding!r} / mode {mode!r}")
+    ext = tuple(x.shape[1:4])
+    pads = [same_pads(i, k, s) if padding == "SAME" else (0, 0) for i, k, s in zip(ext, ksize, strides)]
+    if min(conv_out_size(i, k, s, padding) for i, k, s in zip(ext, ksize, strides)) < 1:
+        raise ValueError(f"pool3d: a {tuple(ksize)} {padding} window over {ext} has an empty output")
+    xn = x.permute(0, 4, 1, 2, 3)
+    flat = (*pads[2], *pads[1], *pads[0])
+    if mode == "max":
+        if any(flat):
+            xn = F.pad(xn, flat, value=float("-inf"))
+        y = F.max_pool3d(xn, tuple(ksize), tuple(strides))
+    elif any(flat):
+        ssum = F.avg_pool3d(F.pad(xn, flat), tuple(ksize), tuple(strides), divisor_override=1)
+        cnt = F.avg_pool3d(F.pad(torch.ones_like(xn[:, :1]), flat), tuple(ksize), tuple(strides), divisor_override=1)
+        y = ssum / cnt
+    else:
+        y = F.avg_pool3d(xn, tuple(ksize), tuple(strides))
+    return y.permute(0, 2, 3, 4, 1).contiguous()
+
+
+def _pool3d(node, x, mode):
+    if node.attr("data_format", "NDHWC") != "NDHWC":
+        raise NotImplementedError(f"{node.op} {node.name}: only NDHWC is supported")
+    k = _dhw(node.attr("ksize"), "NDHWC", f"{node.op} {node.name}: ksize")
+    s = _dhw(node.attr("strides"), "NDHWC", f"{node.op} {node.name}: strides")
+    return (pool3d_tf(x, k, s, node.attr("padding", "VALID"), mode),)
+
+
+@register("MaxPool3D")
+def _maxpool3d(ctx, node, x):
+    return _pool3d(node, x, "max")
+
+
+@register("AvgPool3D")
+def _avgpool3d(ctx, node, x):
+    return _pool3d(node, x, "avg")
+
+
 @register("DepthwiseConv2dNative")
 def _dwconv(ctx, node, x, w):
     fmt = node.attr("data_format", "NHWC")

@@ -65,6 +65,9 @@ class Val:
     # dense prediction heads: a ``ResizeBilinear`` result without a step or a buffer, read only by an
     # ``ArgMax`` that interpolates on the fly: (source Val, align_corners, half_pixel_centers)
     resize_of: tuple | None = None
+    # video models (``conv3d_lowering.py``): the float value of an absorbed ``Cast → Mul | RealDiv`` of a
+    # uint8 clip feed, without a step or a buffer, read only by one ``Conv3D``: (feed Val, scalar factor)
+    u8_of: tuple | None = None
 
     @property
     def is_const(self):

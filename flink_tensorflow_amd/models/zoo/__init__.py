@@ -4,6 +4,7 @@ _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "m
             "UNetModel": "image_classifier", "unet_graph_def": "unet", "export_unet_saved_model": "unet",
             "SSDMobileNetModel": "image_classifier", "ssd_mobilenet_v1_graph_def": "ssd",
             "LSTMClassifierModel": "lstm", "lstm_classifier_graph_def": "lstm",
+            "VideoClassifierModel": "c3d", "c3d_graph_def": "c3d", "export_c3d_saved_model": "c3d",
             "KeywordSpotterModel": "speech", "speech_commands_graph_def": "speech",
             "export_keyword_spotter_saved_model": "speech"}
 

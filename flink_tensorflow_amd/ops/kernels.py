@@ -1004,6 +1004,193 @@ def deconv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | 
     return out
 
 
+# ------------------------------------------------------------------------------ 3-D conv / 3-D pooling
+# tile configurations of ``conv3d_ndhwc_bf16`` (kernels/conv3d.hip); -1 = the launcher's choice
+CONV3D_TILES = {"128x128": 0, "256x64": 1}
+
+
+def conv3d_eligible(Cin: int, Cout: int, kernel, stride, dilation=(1, 1, 1)) -> bool:
+    """What ``conv3d_ndhwc_bf16`` takes: 8-channel vectors on both sides, filter extents 1..7,
+    strides 1..4, no dilation."""
+    return (Cin > 0 and Cin % 8 == 0 and Cout > 0 and Cout % 8 == 0 and len(kernel) == 3 and len(stride) == 3
+            and all(1 <= k <= 7 for k in kernel) and all(1 <= s <= 4 for s in stride) and tuple(dilation) == (1, 1, 1))
+
+
+def conv3d_pack_weights(w: torch.Tensor) -> torch.Tensor:
+    """TF's ``[KD, KH, KW, Cin, Cout]`` filter as the ``[Cout, KD * KH * KW * Cin]`` matrix the
+    kernel reads: K-contiguous rows, taps in (kd, kh, kw) order.  Same dtype and device as ``w``."""
+    KD, KH, KW, Cin, Cout = w.shape
+    return w.permute(4, 0, 1, 2, 3).reshape(Cout, KD * KH * KW * Cin).contiguous()
+
+
+def conv3d_unpack_weights(w_packed: torch.Tensor, kernel, Cin: int) -> torch.Tensor:
+    """Inverse of ``conv3d_pack_weights``: the ``[KD, KH, KW, Cin, Cout]`` filter."""
+    KD, KH, KW = kernel
+    return w_packed.reshape(w_packed.shape[0], KD, KH, KW, Cin).permute(1, 2, 3, 4, 0).contiguous()
+
+
+def _out3d(name: str, ext, k, s, pad):
+    """Output extents of a window ``k`` / stride ``s`` over ``ext`` with the six ``pad`` values
+    (front, back, top, bottom, left, right)."""
+    if len(pad) != 6 or min(pad) < 0:
+        raise ValueError(f"{name}: pad must be six non-negative values (front, back, top, bottom, left, right)")
+    return tuple((ext[a] + pad[2 * a] + pad[2 * a + 1] - k[a]) // s[a] + 1 for a in range(3))
+
+
+def _out3d_target(name, x, out, out_channel_offset, N, O, C):
+    """The output tensor of a 3-D launcher and its channel offset, checked."""
+    if out is None:
+        out = torch.empty((N, *O, C), dtype=x.dtype if x.is_cuda else torch.float32, device=x.device)
+        out_channel_offset = 0
+    if out.dim() != 5 or tuple(out.shape[:4]) != (N, *O) or out_channel_offset < 0 or out_channel_offset + C > out.shape[4]:
+        raise ValueError(f"{name}: out {tuple(out.shape)} cannot hold [{N},{O[0]},{O[1]},{O[2]},{C}] at offset "
+                         f"{out_channel_offset}")
+    if x.is_cuda and (out.shape[4] % 8 or out_channel_offset % 8):
+        raise ValueError(f"{name}: output row pitch and channel offset must be multiples of 8")
+    return out, out_channel_offset
+
+
+def conv3d_ndhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor | None, kernel, stride=(1, 1, 1),
+                 pad=(0, 0, 0, 0, 0, 0), act=None, out: torch.Tensor | None = None, out_channel_offset: int = 0,
+                 cfg: int = -1) -> torch.Tensor:
+    """NDHWC 3-D conv ``act(conv3d(x, w) + bias)``: ``y[n, od, oh, ow, co] = sum x[n, od sd + kd - pf,
+    oh sh + kh - pt, ow sw + kw - pl, ci] w[co, (kd, kh, kw), ci]`` over the taps inside ``x``.
+
+    ``w_packed`` is ``[Cout, KD * KH * KW * Cin]`` from ``conv3d_pack_weights``; ``pad`` is (front,
+    back, top, bottom, left, right).  With ``out`` given, the result is written at channel offset
+    ``out_channel_offset`` of it.  ``cfg`` pins a tile configuration (``CONV3D_TILES``):
+    measurement and tests only."""
+    a = act_code(act)
+    if a not in (ACT_NONE, ACT_RELU, ACT_RELU6):
+        raise ValueError("conv3d_ndhwc: act must be none, relu or relu6")
+    if x.dim() != 5 or w_packed.dim() != 2:
+        raise ValueError("conv3d_ndhwc: x must be [N, D, H, W, Cin] and w_packed [Cout, K]")
+    N, D, H, W, Cin = x.shape
+    k, s = tuple(int(v) for v in kernel), tuple(int(v) for v in stride)
+    pad = tuple(int(v) for v in pad)
+    if len(k) != 3 or len(s) != 3 or min(k) < 1:
+        raise ValueError("conv3d_ndhwc: kernel and stride are (depth, height, width) triples")
+    Cout, taps = w_packed.shape[0], k[0] * k[1] * k[2]
+    if min(N, D, H, W, Cin) < 1 or w_packed.shape[1] != taps * Cin:
+        raise ValueError(f"conv3d_ndhwc: packed weights {tuple(w_packed.shape)} do not match a {k} filter over {Cin} "
+                         "input channels")
+    if not conv3d_eligible(Cin, Cout, k, s):
+        raise ValueError(f"conv3d_ndhwc: unsupported Cin={Cin}, Cout={Cout}, filter {k}, stride {s}")
+    O = _out3d("conv3d_ndhwc", (D, H, W), k, s, pad)
+    if any(pad[2 * i] >= k[i] for i in range(3)):
+        raise ValueError(f"conv3d_ndhwc: pads {pad} must be below the filter size {k}")
+    if min(O) < 1:
+        raise ValueError("conv3d_ndhwc: empty output")
+    if N * O[0] * O[1] * O[2] >= 2 ** 31:
+        raise ValueError("conv3d_ndhwc: more than 2^31 output pixels")
+    if cfg not in (-1, *CONV3D_TILES.values()):
+        raise ValueError(f"conv3d_ndhwc: unknown tile configuration {cfg}")
+    out, out_channel_offset = _out3d_target("conv3d_ndhwc", x, out, out_channel_offset, N, O, Cout)
+    if bias is not None and bias.numel() != Cout:
+        raise ValueError("conv3d_ndhwc: bias must have Cout elements")
+    if x.is_cuda:
+        for t, n in ((x, "x"), (w_packed, "w_packed"), (out, "out")):
+            _check(t, n, device=x.device)
+        if bias is not None:
+            _check(bias, "bias", torch.float32, x.device)
+        else:
+            bias = _zeros_bias(Cout, x.device)
+        _hip().conv3d_ndhwc_bf16(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), N, D, H, W, Cin,
+                                 *O, Cout, *k, *s, pad[0], pad[2], pad[4], a, out.shape[4], out_channel_offset,
+                                 w_packed.numel(), cfg, _stream())
+        return out
+    # host reference, tap by tap from the packed layout, as the kernel walks it
+    xf = x.float()
+    wm = w_packed.float().reshape(Cout, taps, Cin)
+    y = torch.zeros((N, *O, Cout), dtype=torch.float32)
+    ext = (D, H, W)
+    t = 0
+    for kd in range(k[0]):
+        for kh in range(k[1]):
+            for kw in range(k[2]):
+                # output o of an axis reads input o * s + tap - pad where that is inside x
+                rng = []
+                for ax, tap in enumerate((kd, kh, kw)):
+                    off = tap - pad[2 * ax]
+                    lo = max(0, -(off // s[ax]))
+                    hi = min(O[ax], (ext[ax] - 1 - off) // s[ax] + 1)
+                    rng.append((lo, hi, off))
+                if all(lo < hi for lo, hi, _ in rng):
+                    (d0, d1, do), (h0, h1, ho), (w0, w1, wo) = rng
+                    xs = xf[:, d0 * s[0] + do:(d1 - 1) * s[0] + do + 1:s[0], h0 * s[1] + ho:(h1 - 1) * s[1] + ho + 1:s[1],
+                            w0 * s[2] + wo:(w1 - 1) * s[2] + wo + 1:s[2]]
+                    y[:, d0:d1, h0:h1, w0:w1] += xs @ wm[:, t].t()
+                t += 1
+    if bias is not None:
+        y = y + bias.float()
+    y = _apply_act_ref(y, a)
+    out[..., out_channel_offset:out_channel_offset + Cout] = y.to(out.dtype)
+    return out
+
+
+def pool3d_eligible(C: int, ksize, stride) -> bool:
+    """What ``pool3d_ndhwc_bf16`` takes: 8-channel vectors, window extents and strides 1..8."""
+    return (C > 0 and C % 8 == 0 and len(ksize) == 3 and len(stride) == 3 and all(1 <= k <= 8 for k in ksize)
+            and all(1 <= s <= 8 for s in stride))
+
+
+def pool3d_ndhwc(x: torch.Tensor, ksize, stride, pad=(0, 0, 0, 0, 0, 0), mode: str = "max",
+                 out: torch.Tensor | None = None, out_channel_offset: int = 0) -> torch.Tensor:
+    """NDHWC 3-D max / average pooling; ``pad`` is (front, back, top, bottom, left, right).
+    Window elements outside ``x`` take no part: they never win a max, and an average divides by
+    the number of elements inside.  With ``out`` given, the result is written at channel offset
+    ``out_channel_offset`` of it."""
+    if mode not in ("max", "avg"):
+        raise ValueError("pool3d_ndhwc: mode must be max or avg")
+    if x.dim() != 5:
+        raise ValueError("pool3d_ndhwc: x must be [N, D, H, W, C]")
+    N, D, H, W, C = x.shape
+    k, s = tuple(int(v) for v in ksize), tuple(int(v) for v in stride)
+    pad = tuple(int(v) for v in pad)
+    if min(N, D, H, W, C) < 1 or not pool3d_eligible(C, k, s):
+        raise ValueError(f"pool3d_ndhwc: unsupported C={C}, window {k}, stride {s}")
+    O = _out3d("pool3d_ndhwc", (D, H, W), k, s, pad)
+    if any(pad[2 * i] >= k[i] for i in range(3)):
+        raise ValueError(f"pool3d_ndhwc: pads {pad} must be below the window size {k}")
+    if min(O) < 1:
+        raise ValueError("pool3d_ndhwc: empty output")
+    if any((O[i] - 1) * s[i] - pad[2 * i] >= (D, H, W)[i] for i in range(3)):
+        raise ValueError("pool3d_ndhwc: a window lies outside the input")
+    out, out_channel_offset = _out3d_target("pool3d_ndhwc", x, out, out_channel_offset, N, O, C)
+    if x.is_cuda:
+        _check(x, "x", device=x.device)
+        _check(out, "out", device=x.device)
+        _hip().pool3d_ndhwc_bf16(x.data_ptr(), out.data_ptr(), N, D, H, W, C, *O, *k, *s, pad[0], pad[2], pad[4],
+                                 1 if mode == "avg" else 0, out.shape[4], out_channel_offset, _stream())
+        return out
+    # host reference: window element by window element, outside elements predicated out
+    xf = x.float()
+    acc = torch.full((N, *O, C), float("-inf") if mode == "max" else 0.0)
+    cnt = torch.zeros((1, *O, 1))
+    ext = (D, H, W)
+    for i in range(k[0]):
+        for j in range(k[1]):
+            for l in range(k[2]):
+                rng = []
+                for ax, tap in enumerate((i, j, l)):
+                    off = tap - pad[2 * ax]
+                    rng.append((max(0, -(off // s[ax])), min(O[ax], (ext[ax] - 1 - off) // s[ax] + 1), off))
+                if not all(lo < hi for lo, hi, _ in rng):
+                    continue
+                (d0, d1, do), (h0, h1, ho), (w0, w1, wo) = rng
+                xs = xf[:, d0 * s[0] + do:(d1 - 1) * s[0] + do + 1:s[0], h0 * s[1] + ho:(h1 - 1) * s[1] + ho + 1:s[1],
+                        w0 * s[2] + wo:(w1 - 1) * s[2] + wo + 1:s[2]]
+                sub = acc[:, d0:d1, h0:h1, w0:w1]
+                if mode == "max":
+                    torch.maximum(sub, xs, out=sub)
+                else:
+                    sub += xs
+                    cnt[:, d0:d1, h0:h1, w0:w1] += 1
+    y = acc / cnt if mode == "avg" else acc
+    out[..., out_channel_offset:out_channel_offset + C] = y.to(out.dtype)
+    return out
+
+
 # ------------------------------------------------------------------------------ bilinear resize / ArgMax
 # kernel of ``resize_argmax_nhwc`` (kernels/resize.hip); 0 = the launcher's choice
 RESIZE_ARGMAX_PATHS = {"staged": 1, "simple": -1}
