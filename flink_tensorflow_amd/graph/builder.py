@@ -193,6 +193,53 @@ class GraphBuilder:
     def sigmoid(self, x, name=None) -> str:
         return self.op("Sigmoid", [x], name=name)
 
+    def tanh(self, x, name=None) -> str:
+        return self.op("Tanh", [x], name=name)
+
+    def clip_by_value(self, x, lo, hi, name=None) -> str:
+        nm = name or "clip_by_value"
+        lo_c = self.constant(f"{nm}/clip_value_min", np.asarray(lo, dtype=np.float32))
+        hi_c = self.constant(f"{nm}/clip_value_max", np.asarray(hi, dtype=np.float32))
+        return self.op("ClipByValue", [x, lo_c, hi_c], name=nm)
+
+    def pad(self, x, paddings, value=0, name=None) -> str:
+        """``Pad`` of ``x`` by ``paddings [rank, 2]``; a ``value`` other than 0 makes it a ``PadV2``."""
+        nm = name or "Pad"
+        p = self.constant(f"{nm}/paddings", np.asarray(paddings, dtype=np.int32).reshape(-1, 2))
+        if value == 0:
+            return self.op("Pad", [x, p], name=nm, Tpaddings=DataType.INT32)
+        cv = self.constant(f"{nm}/constant_values", np.asarray(value, dtype=np.float32))
+        return self.op("PadV2", [x, p, cv], name=nm, Tpaddings=DataType.INT32)
+
+    def mirror_pad(self, x, paddings, mode="REFLECT", name=None) -> str:
+        """``MirrorPad`` of ``x`` by ``paddings [rank, 2]``; ``mode`` is ``REFLECT`` or ``SYMMETRIC``."""
+        if mode not in ("REFLECT", "SYMMETRIC"):
+            raise ValueError(f"mirror_pad: mode {mode!r} is not REFLECT or SYMMETRIC")
+        nm = name or "MirrorPad"
+        p = self.constant(f"{nm}/paddings", np.asarray(paddings, dtype=np.int32).reshape(-1, 2))
+        return self.op("MirrorPad", [x, p], name=nm, mode=mode.encode(), Tpaddings=DataType.INT32)
+
+    def instance_norm(self, x, gamma, beta, eps=1e-6, name="InstanceNorm") -> str:
+        """``tf.contrib.layers.instance_norm`` of NHWC ``x`` node for node: ``nn.moments(x, [1, 2],
+        keep_dims=True)`` and ``nn.batch_normalization`` (the form of ``bert_graph.layer_norm`` with
+        the two spatial axes).  ``gamma`` / ``beta`` are tensor names of ``[C]`` values."""
+        with self.name_scope(name):
+            axes = self.constant("moments/mean/reduction_indices", np.asarray([1, 2], np.int32))
+            mean = self.op("Mean", [x, axes], name="moments/mean", keep_dims=True, T=DataType.FLOAT, Tidx=DataType.INT32)
+            sg = self.op("StopGradient", [mean], name="moments/StopGradient", T=DataType.FLOAT)
+            sq = self.op("SquaredDifference", [x, sg], name="moments/SquaredDifference", T=DataType.FLOAT)
+            axes2 = self.constant("moments/variance/reduction_indices", np.asarray([1, 2], np.int32))
+            var = self.op("Mean", [sq, axes2], name="moments/variance", keep_dims=True, T=DataType.FLOAT,
+                          Tidx=DataType.INT32)
+            e = self.constant("instancenorm/add/y", np.float32(eps))
+            ve = self.add(var, e, name="instancenorm/add")
+            rs = self.op("Rsqrt", [ve], name="instancenorm/Rsqrt", T=DataType.FLOAT)
+            inv = self.mul(rs, gamma, name="instancenorm/mul")
+            xm = self.mul(x, inv, name="instancenorm/mul_1")
+            mm = self.mul(mean, inv, name="instancenorm/mul_2")
+            sh = self.sub(beta, mm, name="instancenorm/sub")
+            return self.add(xm, sh, name="instancenorm/add_1")
+
     def exp(self, x, name=None) -> str:
         return self.op("Exp", [x], name=name)
 

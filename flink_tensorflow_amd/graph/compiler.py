@@ -34,6 +34,11 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    * ``[Cast(INT16) → Mul|RealDiv] → [Transpose] → AudioSpectrogram → Mfcc → [Reshape]`` → one
      ``mfcc`` step from PCM to coefficients (kernels/audio.hip, ``audio_lowering.py``); a lone
      ``AudioSpectrogram`` → one ``spectrogram`` step;
+   * ``moments(x, [1, 2]) + batch_normalization`` (``tf.contrib.layers.instance_norm``) ``→ [Relu|Relu6]`` → one
+     ``instnorm`` step (kernels/instnorm.hip); ``MirrorPad`` / ``Pad`` / ``PadV2`` of the spatial axes → one ``pad``
+     step; ``[Tanh|Sigmoid] → [Mul] → [Add|Sub] → [ClipByValue] → [Cast(UINT8)]`` behind a 1, 3 or 4 channel conv →
+     one ``image_out`` step that writes the compact fp32 or uint8 image (kernels/pad.hip,
+     ``generator_lowering.py``);
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -47,7 +52,7 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is eleven modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+The compiler is twelve modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
 map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
 pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
 ``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
@@ -55,6 +60,7 @@ mixin: box decoding + NMS), ``recurrent_lowering.py`` (the ``RecurrentLowering``
 ops around it), ``audio_lowering.py`` (the ``AudioLowering`` mixin: the spectrogram / MFCC front end and the
 ops it absorbs), ``deconv_lowering.py`` (the ``DeconvLowering`` mixin: ``Conv2DBackpropInput`` chains),
 ``conv3d_lowering.py`` (the ``Conv3DLowering`` mixin: ``Conv3D`` chains, 3-D pools, uint8 clips),
+``generator_lowering.py`` (the ``GeneratorLowering`` mixin: instance norm, spatial pads, the image output stage),
 ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
 ``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
 bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
@@ -90,6 +96,7 @@ from .conv3d_lowering import Conv3DLowering
 from .conv_lowering import _ACTS, ConvLowering
 from .deconv_lowering import DeconvLowering
 from .detection_lowering import _UNPADDED_NMS, DetectionLowering
+from .generator_lowering import _IMAGE_OUT_OPS, _PAD_OPS, GeneratorLowering
 from .graph import Graph, Node
 from .op_registry import OpContext, lookup
 from .ops_nn import same_pads
@@ -119,8 +126,8 @@ class _ConstSession:
         self._const_cache = {}
 
 
-class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering, DeconvLowering,
-                       Conv3DLowering, ConvLowering, PlanMemory, PlanRunner):
+class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering,
+                       DeconvLowering, Conv3DLowering, ConvLowering, PlanMemory, PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -418,6 +425,10 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
             return self._lower_conv3d(node)
         if op in ("MaxPool3D", "AvgPool3D"):
             return self._lower_pool3d(node)
+        if op in _PAD_OPS:
+            return self._lower_pad(node)
+        if op in _IMAGE_OUT_OPS and self._lower_image_out(node):
+            return
         if op == "MatMul":
             return self._lower_matmul(node)
         if op == "Cast" and self._try_preprocess(node):
@@ -941,23 +952,31 @@ class CompiledFunction(TransformerLowering, DetectionLowering, RecurrentLowering
         self.vals[(node.name, 0)] = out
 
     def _concat_writable(self, v: Val, src_node: str, concat_node: str) -> bool:
-        # produced by exactly one conv/pool/resize/deconv/conv3d/pool3d step (which can write at a channel offset),
+        # produced by exactly one conv/pool/resize/deconv/conv3d/pool3d/instnorm/pad step (which can write at a channel offset),
         # consumed by nothing but this concat, and not fetched
         prods = [s for s in self.steps if any(o is v for o in s.outputs)]
         if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize", "deconv",
-                                                        "conv3d", "pool3d") \
+                                                        "conv3d", "pool3d", "instnorm", "pad") \
                 or v.concat_slot is not None \
                 or (len(prods[0].outputs) != 1 and not prods[0].meta.get("multi_out")):
             return False
         if v.alias_of is not None or v.phys_c:
             return False
         # every graph node that maps to this value must feed only the concat
+        # (a fused reader is a member of the producer's own chain, except the members of a matched norm
+        # group: those read the value as the group's input, and its kernel reads a buffer of its own)
         readers = self._readers(v)
-        if readers is None or any(c != concat_node and c not in self._fused for c in readers):
+        if readers is None or any(c != concat_node and (c not in self._fused or self._norm_group_reads(c, v))
+                                  for c in readers):
             return False
         if v.qscale is not None:
             return v.shape[-1] % 16 == 0 and src_node in self.cons
         return v.shape[-1] % 8 == 0 and v.dtype == torch.bfloat16 and src_node in self.cons
+
+    def _norm_group_reads(self, name: str, v: Val) -> bool:
+        """Graph node ``name`` belongs to a matched ``ln`` group whose input is the value ``v``."""
+        grp = self._groups.get(name)
+        return grp is not None and grp["kind"] == "ln" and self.vals.get(grp["x"]) is v
 
     def _lower_glue(self, node: Node, host_consts=()):
         """``node`` as a captured interpreter op.  ``host_consts``: the inputs whose constants stay on

@@ -202,8 +202,8 @@ class ConvLowering:
                 shift = b - m * s
                 scale = s if scale is None else scale * s
                 bias = shift if bias is None else bias * s + shift
-            elif nxt.op in acts and act == K.ACT_NONE:
-                act = acts[nxt.op]
+            elif nxt.op in acts and act == K.ACT_NONE and not self._image_out_keeps(start, nxt):
+                act = acts[nxt.op]  # (a Tanh / Sigmoid that heads an image-output chain is that step's)
             else:
                 break
             absorbed.append(nxt)

@@ -409,17 +409,47 @@ def _tile(ctx, node, x, multiples):
     return (x.repeat(*_ints(multiples)),)
 
 
-@register("Pad", "PadV2", "MirrorPad")
+@register("Pad", "PadV2")
 def _pad(ctx, node, x, paddings, *cv):
     p = np.asarray(_ints(paddings)).reshape(-1, 2)
     flat = []
     for lo, hi in p[::-1]:
         flat += [int(lo), int(hi)]
-    if node.op == "MirrorPad":
-        mode = "reflect" if node.attr("mode", "REFLECT") == "REFLECT" else "replicate"
-        return (F.pad(x, flat, mode=mode),)
     value = cv[0].item() if cv else 0
     return (F.pad(x, flat, value=value),)
+
+
+@register("MirrorPad")
+def _mirror_pad(ctx, node, x, paddings):
+    """TF ``MirrorPad`` of any rank, ``paddings [rank, 2]``, by one index gather per axis.  Output
+    index ``i`` of an axis of ``size`` padded by ``(lo, hi)`` reads ``r = i - lo`` when ``0 <= r <
+    size``, and otherwise
+
+    * ``REFLECT``:   ``-r`` below, ``2 (size - 1) - r`` above (the edge element is not repeated;
+      ``lo, hi <= size - 1``);
+    * ``SYMMETRIC``: ``-r - 1`` below, ``2 size - 1 - r`` above (the edge element is repeated;
+      ``lo, hi <= size``).
+
+    A larger pad is a ``ValueError`` naming the axis, as TF rejects it."""
+    mode = node.attr("mode", "REFLECT")
+    mode = mode.decode() if isinstance(mode, bytes) else mode
+    if mode not in ("REFLECT", "SYMMETRIC"):
+        raise ValueError(f"MirrorPad {node.name}: mode {mode!r} is not REFLECT or SYMMETRIC")
+    p = np.asarray(_ints(paddings)).reshape(-1, 2)
+    if p.shape[0] != x.dim():
+        raise ValueError(f"MirrorPad {node.name}: paddings {p.shape} do not match rank {x.dim()}")
+    off = 1 if mode == "REFLECT" else 0
+    for axis, (lo, hi) in enumerate(p.tolist()):
+        size = x.shape[axis]
+        if lo < 0 or hi < 0 or max(lo, hi) > size - off:
+            raise ValueError(f"MirrorPad {node.name}: paddings ({lo}, {hi}) of axis {axis} must be at most "
+                             f"{size - off} in {mode} mode (the axis has {size} elements)")
+        if lo == 0 and hi == 0:
+            continue
+        r = torch.arange(-lo, size + hi, device=x.device)
+        src = torch.where(r < 0, -r - 1 + off, torch.where(r >= size, 2 * size - 1 - off - r, r))
+        x = x.index_select(axis, src)
+    return (x,)
 
 
 @register("Slice")

@@ -34,6 +34,8 @@ void register_lstm(pybind11::module_& m);
 void register_audio(pybind11::module_& m);
 void register_deconv(pybind11::module_& m);
 void register_conv3d(pybind11::module_& m);
+void register_instnorm(pybind11::module_& m);
+void register_pad(pybind11::module_& m);
 
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "flink_tensorflow_amd CDNA4 (gfx950) kernels";
@@ -63,6 +65,8 @@ PYBIND11_MODULE(_hip, m) {
   register_audio(m);
   register_deconv(m);
   register_conv3d(m);
+  register_instnorm(m);
+  register_pad(m);
   // Streams owned by the framework (not torch's round-robin pool of 32 per device): a pooled
   // stream handed to a runner can be the very stream another thread is capturing a hipGraph
   // on, and then that thread's launches land in the capture (or are rejected).

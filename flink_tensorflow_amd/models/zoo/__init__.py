@@ -6,7 +6,9 @@ _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "m
             "LSTMClassifierModel": "lstm", "lstm_classifier_graph_def": "lstm",
             "VideoClassifierModel": "c3d", "c3d_graph_def": "c3d", "export_c3d_saved_model": "c3d",
             "KeywordSpotterModel": "speech", "speech_commands_graph_def": "speech",
-            "export_keyword_spotter_saved_model": "speech"}
+            "export_keyword_spotter_saved_model": "speech",
+            "StyleTransferModel": "style_transfer", "style_transfer_graph_def": "style_transfer",
+            "export_style_transfer_saved_model": "style_transfer"}
 
 __all__ = sorted(_EXPORTS)
 

@@ -1281,6 +1281,204 @@ def resize_argmax_nhwc(x: torch.Tensor, out_hw=None, align_corners: bool = False
     return out
 
 
+# ------------------------------------------------------------------------------ generators: instance norm, pad, image out
+_IN_ACTS = (ACT_NONE, ACT_RELU, ACT_RELU6)
+_IN_THREADS, _IN_PT = 256, 8  # kernels/instnorm.hip: threads per workgroup, pixels a thread holds
+PAD_MODES = {"constant": 0, "reflect": 1, "symmetric": 2}
+IMAGE_OUT_ACTS = {None: 0, "none": 0, "tanh": 1, "sigmoid": 2}
+
+
+def instance_norm_eligible(H: int, W: int, C: int) -> bool:
+    """What ``instance_norm`` takes (the lowering asks before it emits an ``instnorm`` step)."""
+    return C >= 8 and C % 8 == 0 and H >= 1 and W >= 1
+
+
+def _in_chunks(H: int, W: int, C: int) -> int:
+    rows = _IN_THREADS // min(C // 8, _IN_THREADS)
+    return -(-(H * W) // (rows * _IN_PT))
+
+
+def instance_norm_scratch_numel(N: int, H: int, W: int, C: int) -> int:
+    """fp32 elements of the scratch ``instance_norm`` needs: the per-chunk partials ``[N, chunks,
+    C, 2]`` (mean, M2) and, behind them, the statistics ``[N, C, 2]`` (mean, gamma / sqrt(var + eps))."""
+    if not instance_norm_eligible(H, W, C) or N < 1:
+        raise ValueError(f"instance_norm: shape [{N},{H},{W},{C}] outside the kernel's envelope (C % 8 == 0)")
+    return N * _in_chunks(H, W, C) * C * 2 + N * C * 2
+
+
+def instance_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, act=None,
+                  out: torch.Tensor | None = None, out_channel_offset: int = 0,
+                  scratch: torch.Tensor | None = None) -> torch.Tensor:
+    """Instance normalisation of an NHWC activation: ``act((x - m) * rsqrt(v + eps) * gamma + beta)``
+    with ``m`` / ``v`` the mean and the biased variance over the ``H W`` pixels of one image and
+    channel.  ``x`` is bf16, the arithmetic fp32 with centred statistics, one rounding at the store.
+    ``act`` is none, relu or relu6.  With ``out`` given, the ``C`` result channels are written at
+    channel offset ``out_channel_offset`` of it (a concat slot).  ``scratch`` is an fp32 tensor of
+    ``instance_norm_scratch_numel`` elements: a captured launch passes it, so nothing is allocated."""
+    if x.dim() != 4:
+        raise ValueError(f"instance_norm: x must be [N, H, W, C], got {tuple(x.shape)}")
+    N, H, W, C = x.shape
+    if N < 1 or not instance_norm_eligible(H, W, C):
+        raise ValueError(f"instance_norm: shape {tuple(x.shape)} outside the kernel's envelope (C % 8 == 0, no empty axis)")
+    a = act_code(act)
+    if a not in _IN_ACTS:
+        raise ValueError(f"instance_norm: activation {act!r} is not none, relu or relu6")
+    if tuple(gamma.shape) != (C,) or tuple(beta.shape) != (C,):
+        raise ValueError(f"instance_norm: gamma {tuple(gamma.shape)} / beta {tuple(beta.shape)} are not [{C}]")
+    if gamma.dtype != torch.float32 or beta.dtype != torch.float32:
+        raise TypeError(f"instance_norm: gamma / beta are fp32, not {gamma.dtype} / {beta.dtype}")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"instance_norm: x is bf16, not {x.dtype}")
+    if not float(eps) >= 0.0:
+        raise ValueError(f"instance_norm: eps {eps!r} is negative")
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+        out_channel_offset = 0
+    if out.dim() != 4 or tuple(out.shape[:3]) != (N, H, W) or out_channel_offset < 0 \
+            or out_channel_offset + C > out.shape[3]:
+        raise ValueError(f"instance_norm: out {tuple(out.shape)} cannot hold [{N},{H},{W},{C}] at offset "
+                         f"{out_channel_offset}")
+    if out.shape[3] % 8 or out_channel_offset % 8:
+        raise ValueError("instance_norm: output row pitch and channel offset must be multiples of 8")
+    if x.is_cuda:
+        dev = x.device
+        _check(x, "x", device=dev)
+        _check(out, "out", device=dev)
+        _check(gamma, "gamma", torch.float32, dev)
+        _check(beta, "beta", torch.float32, dev)
+        need = instance_norm_scratch_numel(N, H, W, C)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        _check(scratch, "scratch", torch.float32, dev)
+        if scratch.numel() < need:
+            raise ValueError(f"instance_norm: scratch has {scratch.numel()} fp32 elements, {need} needed")
+        _hip().instance_norm_nhwc_bf16(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
+                                       scratch.data_ptr(), scratch.numel(), N, H, W, C, out.shape[3],
+                                       out_channel_offset, float(eps), a, _stream())
+        return out
+    xf = x.float()
+    m = xf.mean((1, 2), keepdim=True)
+    d = xf - m
+    v = (d * d).mean((1, 2), keepdim=True)
+    y = _apply_act_ref(d * (gamma / torch.sqrt(v + float(eps))) + beta, a)
+    out[..., out_channel_offset:out_channel_offset + C] = y.to(out.dtype)
+    return out
+
+
+def mirror_index(size: int, lo: int, hi: int, mode: str) -> torch.Tensor:
+    """Source indices of an axis of ``size`` padded by ``lo`` / ``hi``: output ``i`` reads ``r = i -
+    lo`` inside the axis, else ``-r`` / ``2 (size - 1) - r`` (reflect), ``-r - 1`` / ``2 size - 1 - r``
+    (symmetric); constant mode marks the outside ``-1``."""
+    r = torch.arange(-lo, size + hi)
+    if mode == "reflect":
+        return torch.where(r < 0, -r, torch.where(r >= size, 2 * (size - 1) - r, r))
+    if mode == "symmetric":
+        return torch.where(r < 0, -r - 1, torch.where(r >= size, 2 * size - 1 - r, r))
+    return torch.where((r < 0) | (r >= size), -1, r)
+
+
+def pad_nhwc(x: torch.Tensor, pads, mode: str = "constant", value: float = 0.0, out: torch.Tensor | None = None,
+             out_channel_offset: int = 0, channels: int | None = None) -> torch.Tensor:
+    """TF ``Pad`` / ``PadV2`` (``mode="constant"``) or ``MirrorPad`` (``"reflect"``, ``"symmetric"``)
+    of the two spatial axes of a bf16 NHWC activation; ``pads = (top, bottom, left, right)``.  A
+    reflect pad is at most ``size - 1``, a symmetric one at most ``size``.  All ``x.shape[-1]``
+    physical channels are copied; ``channels`` is the logical ``C`` of a channel-padded ``x``: a
+    constant fill writes ``value`` to those and zero to the padding.  With ``out`` given the result is
+    written at channel offset ``out_channel_offset`` of it (a concat slot)."""
+    if x.dim() != 4:
+        raise ValueError(f"pad_nhwc: x must be [N, H, W, C], got {tuple(x.shape)}")
+    if mode not in PAD_MODES:
+        raise ValueError(f"pad_nhwc: mode {mode!r} is not one of {sorted(PAD_MODES)}")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"pad_nhwc: x is bf16, not {x.dtype}")
+    N, H, W, C = x.shape
+    Cl = C if channels is None else int(channels)
+    if len(pads) != 4 or any(int(p) != p or p < 0 for p in pads):
+        raise ValueError(f"pad_nhwc: pads {pads!r} are not four non-negative integers (top, bottom, left, right)")
+    pt, pb, pl, pr = (int(p) for p in pads)
+    if min(N, H, W, C) < 1 or C % 8 or not 1 <= Cl <= C:
+        raise ValueError(f"pad_nhwc: shape {tuple(x.shape)} (channels={Cl}) needs C % 8 == 0 and no empty axis")
+    if mode != "constant":
+        lim = 1 if mode == "reflect" else 0
+        for axis, size, lo, hi in ((1, H, pt, pb), (2, W, pl, pr)):
+            if max(lo, hi) > size - lim:
+                raise ValueError(f"pad_nhwc: {mode} pad ({lo}, {hi}) of axis {axis} exceeds {size - lim}")
+    Ho, Wo = H + pt + pb, W + pl + pr
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+        out_channel_offset = 0
+    if out.dim() != 4 or tuple(out.shape[:3]) != (N, Ho, Wo) or out_channel_offset < 0 \
+            or out_channel_offset + C > out.shape[3]:
+        raise ValueError(f"pad_nhwc: out {tuple(out.shape)} cannot hold [{N},{Ho},{Wo},{C}] at offset "
+                         f"{out_channel_offset}")
+    if out.shape[3] % 8 or out_channel_offset % 8:
+        raise ValueError("pad_nhwc: output row pitch and channel offset must be multiples of 8")
+    if x.is_cuda:
+        _check(x, "x", device=x.device)
+        _check(out, "out", device=x.device)
+        _hip().pad_nhwc_bf16(x.data_ptr(), out.data_ptr(), N, H, W, C, Cl, pt, pb, pl, pr, PAD_MODES[mode],
+                             float(value), C, out.shape[3], out_channel_offset, _stream())
+        return out
+    iy, ix = mirror_index(H, pt, pb, mode), mirror_index(W, pl, pr, mode)
+    y = x[:, iy.clamp(min=0)][:, :, ix.clamp(min=0)]
+    if mode == "constant":
+        fill = torch.zeros(C, dtype=x.dtype)
+        fill[:Cl] = torch.tensor(float(value)).to(x.dtype)
+        outside = (iy < 0)[:, None] | (ix < 0)[None, :]
+        y = torch.where(outside[None, :, :, None], fill, y)
+    out[..., out_channel_offset:out_channel_offset + C] = y
+    return out
+
+
+def image_out(x: torch.Tensor, channels: int, act=None, scale: float = 1.0, offset: float = 0.0, clamp=None,
+              dtype=torch.float32, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The output stage of a generator: ``clamp(act(x[..., :channels]) * scale + offset)`` of a bf16
+    NHWC buffer (``x.shape[-1]`` its physical channels) as a compact ``[N, H, W, channels]`` fp32 or
+    uint8 image.  ``channels`` is 1, 3 or 4, ``act`` none / tanh / sigmoid, ``clamp`` None or ``(lo,
+    hi)``.  fp32 arithmetic, every operation rounded on its own; uint8 truncates after the clamp
+    (TF's ``Cast``) and needs a clamp inside ``[0, 255]``."""
+    if x.dim() != 4:
+        raise ValueError(f"image_out: x must be [N, H, W, C], got {tuple(x.shape)}")
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"image_out: x is bf16, not {x.dtype}")
+    N, H, W, ldx = x.shape
+    Cl = int(channels)
+    if Cl not in (1, 3, 4):
+        raise ValueError(f"image_out: channels={channels!r} is not 1, 3 or 4")
+    if min(N, H, W) < 1 or ldx % 8 or ldx < Cl:
+        raise ValueError(f"image_out: x {tuple(x.shape)} needs a pixel pitch that is a multiple of 8 and no empty axis")
+    if act not in IMAGE_OUT_ACTS:
+        raise ValueError(f"image_out: activation {act!r} is not none, tanh or sigmoid")
+    if out is not None:
+        dtype = out.dtype
+    if dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"image_out: the image is fp32 or uint8, not {dtype}")
+    if clamp is not None:
+        lo, hi = (float(v) for v in clamp)
+        if not lo <= hi:
+            raise ValueError(f"image_out: clamp {clamp!r} is empty")
+    if dtype == torch.uint8 and (clamp is None or lo < 0.0 or hi > 255.0):
+        raise ValueError("image_out: a uint8 image needs a clamp inside [0, 255]")
+    if out is None:
+        out = torch.empty((N, H, W, Cl), dtype=dtype, device=x.device)
+    if tuple(out.shape) != (N, H, W, Cl):
+        raise ValueError(f"image_out: out {tuple(out.shape)} is not [{N},{H},{W},{Cl}]")
+    if x.is_cuda:
+        _check(x, "x", device=x.device)
+        _check(out, "out", dtype, x.device)
+        _hip().image_out_bf16(x.data_ptr(), out.data_ptr(), N * H * W, ldx, Cl, IMAGE_OUT_ACTS[act], float(scale),
+                              float(offset), clamp is not None, lo if clamp is not None else 0.0,
+                              hi if clamp is not None else 0.0, 1 if dtype == torch.uint8 else 4, _stream())
+        return out
+    v = x[..., :Cl].float()
+    v = torch.tanh(v) if IMAGE_OUT_ACTS[act] == 1 else torch.sigmoid(v) if IMAGE_OUT_ACTS[act] == 2 else v
+    v = v * torch.tensor(float(scale), dtype=torch.float32) + torch.tensor(float(offset), dtype=torch.float32)
+    if clamp is not None:
+        v = v.clamp(lo, hi)
+    out.copy_(v.to(dtype))  # uint8: truncation, as TF's Cast
+    return out
+
+
 # ------------------------------------------------------------------------------ detection: box decode + NMS
 # The envelope of ``kernels/detection.hip``, from its LDS budget (160 KiB per CU).  The
 # per-class kernel sorts ``N`` rounded up to a power of two 8-byte keys (at most 4096 * 8 B =
