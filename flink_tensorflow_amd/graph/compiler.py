@@ -39,6 +39,8 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
      step; ``[Tanh|Sigmoid] → [Mul] → [Add|Sub] → [ClipByValue] → [Cast(UINT8)]`` behind a 1, 3 or 4 channel conv →
      one ``image_out`` step that writes the compact fp32 or uint8 image (kernels/pad.hip,
      ``generator_lowering.py``);
+   * ``MatMul(u, items) → [BiasAdd | Add(item_bias)] → TopKV2`` → one ``retrieve`` step: the score GEMM and the
+     top-k selection fused, no score matrix (kernels/retrieve.hip, ``retrieval_lowering.py``);
    * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
@@ -52,7 +54,7 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is twelve modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+The compiler is thirteen modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
 map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
 pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
 ``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
@@ -61,6 +63,7 @@ ops around it), ``audio_lowering.py`` (the ``AudioLowering`` mixin: the spectrog
 ops it absorbs), ``deconv_lowering.py`` (the ``DeconvLowering`` mixin: ``Conv2DBackpropInput`` chains),
 ``conv3d_lowering.py`` (the ``Conv3DLowering`` mixin: ``Conv3D`` chains, 3-D pools, uint8 clips),
 ``generator_lowering.py`` (the ``GeneratorLowering`` mixin: instance norm, spatial pads, the image output stage),
+``retrieval_lowering.py`` (the ``RetrievalLowering`` mixin: the score GEMM + top-k of a two-tower model),
 ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
 ``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
 bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
@@ -104,6 +107,7 @@ from .plan import Chain, CompileError, Step, Val, _coff, _eff_scale, _host, _tar
 from .plan_memory import PlanMemory
 from .plan_run import PlanRunner
 from .recurrent_lowering import RecurrentLowering
+from .retrieval_lowering import RetrievalLowering
 from .transformer_lowering import TransformerLowering
 
 __all__ = ["CompiledFunction", "CompileError", "Step", "Val", "compile_signature"]
@@ -127,7 +131,7 @@ class _ConstSession:
 
 
 class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering,
-                       DeconvLowering, Conv3DLowering, ConvLowering, PlanMemory, PlanRunner):
+                       DeconvLowering, Conv3DLowering, RetrievalLowering, ConvLowering, PlanMemory, PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -567,6 +571,8 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
 
     # ---- matmul chain
     def _lower_matmul(self, node: Node):
+        if self._lower_retrieval(node):  # MatMul -> [bias] -> TopKV2: no score matrix (retrieval_lowering.py)
+            return
         a = self._in(node, 0)
         b = self._in(node, 1)
         if not b.is_const or node.attr("transpose_a", False) or len(a.shape) != 2:

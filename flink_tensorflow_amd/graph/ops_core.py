@@ -545,8 +545,13 @@ def _argmin(ctx, node, x, axis):
 @register("TopKV2", "TopK")
 def _topk(ctx, node, x, *k):
     kk = _ints(k[0])[0] if k else node.attr("k")
-    v, i = torch.topk(x, kk, dim=-1, largest=True, sorted=node.attr("sorted", True))
-    return (v, i.to(torch.int32))
+    if not node.attr("sorted", True) or x.is_cuda:
+        # (device tensors keep torch.topk: a GPU plan's glue TopKV2 runs as it did, a full stable sort of a wide row costs more)
+        v, i = torch.topk(x, kk, dim=-1, largest=True, sorted=node.attr("sorted", True))
+        return (v, i.to(torch.int32))
+    # TF orders equal values lower index first; torch.topk leaves that order open, a stable sort pins it
+    v, i = torch.sort(x, dim=-1, descending=True, stable=True)
+    return (v[..., :kk].contiguous(), i[..., :kk].to(torch.int32))
 
 
 @register("Softmax")

@@ -8,7 +8,9 @@ _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "m
             "KeywordSpotterModel": "speech", "speech_commands_graph_def": "speech",
             "export_keyword_spotter_saved_model": "speech",
             "StyleTransferModel": "style_transfer", "style_transfer_graph_def": "style_transfer",
-            "export_style_transfer_saved_model": "style_transfer"}
+            "export_style_transfer_saved_model": "style_transfer",
+            "RetrievalModel": "two_tower", "two_tower_graph_def": "two_tower",
+            "export_two_tower_saved_model": "two_tower"}
 
 __all__ = sorted(_EXPORTS)
 

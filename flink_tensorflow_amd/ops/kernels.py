@@ -1596,6 +1596,97 @@ def combined_nms(boxes: torch.Tensor, scores: torch.Tensor, max_per_class: int, 
     return out
 
 
+# ------------------------------------------------------------------------------ retrieval: score GEMM + top-k
+# The envelope of ``kernels/retrieve.hip``: ``D`` a multiple of 32 up to 256 (the query's
+# K-fragments stay in registers), ``k <= 128`` (a query's candidate buffer of 2 * kpad keys in
+# LDS; 32 queries per workgroup instead of 64 above k = 64), ``N < 2^31`` (the item index is the
+# low word of a key) and at most 2048 chunks (the merge gives a thread 8 chunk lists).
+RETRIEVE_ITEM_TILE = 64
+RETRIEVE_MAX_K = 128
+RETRIEVE_MAX_CHUNKS = 2048
+_RETRIEVE_WORKGROUPS = 512  # query tiles x chunks of the default chunk: two per CU
+
+
+def _retrieve_kpad(k: int) -> int:
+    return 1 << max(0, int(k) - 1).bit_length()
+
+
+def retrieve_eligible(B: int, N: int, D: int, k: int) -> bool:
+    """What ``retrieve_topk`` takes on the GPU (the lowering asks before it emits a ``retrieve`` step)."""
+    return B >= 1 and D % 32 == 0 and 32 <= D <= 256 and 1 <= k <= RETRIEVE_MAX_K and k <= N < 2 ** 31
+
+
+def retrieve_chunk(B: int, N: int, D: int, k: int) -> int:
+    """Default items per workgroup, from the shapes alone: query tiles x chunks come to about
+    two workgroups per CU (256 CUs), in whole item tiles of at least four."""
+    qtiles = -(-B // (32 if k > 64 else 64))
+    chunks = max(1, _RETRIEVE_WORKGROUPS // qtiles)
+    tiles = max(4, -(-N // (chunks * RETRIEVE_ITEM_TILE)))
+    return tiles * RETRIEVE_ITEM_TILE
+
+
+def retrieve_scratch_numel(B: int, N: int, k: int, chunk: int) -> int:
+    """int64 elements of the scratch ``retrieve_topk`` needs: the sorted keys ``[B, chunks, kpad]``."""
+    return B * -(-N // chunk) * _retrieve_kpad(k)
+
+
+def retrieve_topk(q: torch.Tensor, items: torch.Tensor, k: int, bias: torch.Tensor | None = None,
+                  chunk: int | None = None, out=None, scratch: torch.Tensor | None = None, part: int = 0):
+    """The ``k`` best items per query: ``scores = q @ items.T (+ bias)`` in fp32 from the bf16
+    operands, ordered by descending score and, among equal scores, ascending index (TF
+    ``TopKV2``).  ``q`` is ``[B, D]``, ``items`` ``[N, D]``, ``bias`` fp32 ``[N]``.  Returns
+    ``(values [B, k] fp32, indices [B, k] int32)``; the score matrix is never stored.
+
+    ``chunk`` is the items one workgroup scans (a multiple of ``RETRIEVE_ITEM_TILE``; default
+    ``retrieve_chunk``).  ``out`` is the result pair preallocated and ``scratch`` an int64 tensor
+    of ``retrieve_scratch_numel`` elements: a captured launch passes both.  ``part`` (measurement
+    only): 1 runs the scan alone, 2 the merge alone on what a scan left in ``scratch``."""
+    if q.dim() != 2 or items.dim() != 2 or q.shape[1] != items.shape[1]:
+        raise ValueError(f"retrieve_topk: q {tuple(q.shape)} / items {tuple(items.shape)} are not [B,D] / [N,D]")
+    (B, D), N, k = q.shape, items.shape[0], int(k)
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise ValueError(f"retrieve_topk: bias {tuple(bias.shape)} is not ({N},)")
+    if B < 1 or not 1 <= k <= N:
+        raise ValueError(f"retrieve_topk: B={B}, k={k}, N={N}: need B >= 1 and 1 <= k <= N")
+    chunk = retrieve_chunk(B, N, D, k) if chunk is None else int(chunk)
+    if chunk < 1 or chunk % RETRIEVE_ITEM_TILE:
+        raise ValueError(f"retrieve_topk: chunk {chunk} is not a positive multiple of {RETRIEVE_ITEM_TILE}")
+    if not q.is_cuda:
+        s = q.to(torch.bfloat16).float() @ items.to(torch.bfloat16).float().t()
+        if bias is not None:
+            s = s + bias.float()
+        v, i = torch.sort(s, dim=-1, descending=True, stable=True)  # stable: equal scores keep index order
+        res = (v[:, :k].contiguous(), i[:, :k].to(torch.int32).contiguous())
+        if out is None:
+            return res
+        for o, r in zip(out, res):
+            o.copy_(r)
+        return tuple(out)
+    if not retrieve_eligible(B, N, D, k) or -(-N // chunk) > RETRIEVE_MAX_CHUNKS:
+        raise ValueError(f"retrieve_topk: B={B}, N={N}, D={D}, k={k}, chunk={chunk} outside the kernel's envelope "
+                         f"(D % 32 == 0, 32 <= D <= 256, k <= {RETRIEVE_MAX_K}, N < 2^31, <= {RETRIEVE_MAX_CHUNKS} chunks)")
+    dev = q.device
+    _check(q, "q", torch.bfloat16, dev)
+    _check(items, "items", torch.bfloat16, dev)
+    if bias is not None:
+        _check(bias, "bias", torch.float32, dev)
+    if out is None:
+        out = (torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int32, device=dev))
+    for t, name, dt in ((out[0], "out values", torch.float32), (out[1], "out indices", torch.int32)):
+        _check(t, name, dt, dev)
+        if tuple(t.shape) != (B, k):
+            raise ValueError(f"retrieve_topk: {name} {tuple(t.shape)} is not {(B, k)}")
+    need = retrieve_scratch_numel(B, N, k, chunk)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.int64, device=dev)
+    _check(scratch, "scratch", torch.int64, dev)
+    if scratch.numel() < need:
+        raise ValueError(f"retrieve_topk: scratch has {scratch.numel()} int64 elements, {need} needed")
+    _hip().retrieve_topk(q.data_ptr(), items.data_ptr(), _ptr(bias), B, N, D, k, chunk, scratch.data_ptr(),
+                         scratch.numel(), out[0].data_ptr(), out[1].data_ptr(), int(part), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------ LSTM recurrence
 LSTM_MAX_HIDDEN = 512
 LSTM_RESIDENT_HIDDEN = 128  # up to here the recurrent weights stay in registers for all steps
