@@ -353,6 +353,30 @@ class GraphBuilder:
         kk = self.constant(f"{(name or 'TopKV2')}/k", np.asarray(k, dtype=np.int32))
         return self.op("TopKV2", [x, kk], name=name, sorted=True)
 
+    def embedding_lookup(self, table, ids, name=None) -> str:
+        """``tf.nn.embedding_lookup``: ``GatherV2(table [V, D], ids, axis 0)``."""
+        nm = name or "embedding_lookup"
+        ax = self.constant(f"{nm}/axis", np.asarray(0, dtype=np.int32))
+        return self.op("GatherV2", [table, ids, ax], name=nm, Tparams=DataType.FLOAT, Tindices=DataType.INT32,
+                       Taxis=DataType.INT32, batch_dims=0)
+
+    def dot_interaction(self, vectors, self_interaction=False, concat_with=None, name="interaction") -> str:
+        """DLRM's pairwise dot interaction of ``M`` vectors ``[B, D]``: ``Pack(axis=1)`` to ``T [B, M,
+        D]``, ``BatchMatMul(T, T, adj_y=True)``, ``Reshape`` to ``[B, M * M]`` and a ``GatherV2(axis=1)``
+        of the strict lower triangle (with the diagonal under ``self_interaction``) in row-major
+        order; ``concat_with`` (one of ``vectors``, by name) is concatenated in front.  Emitted in
+        one fixed form, which ``graph/ranking_lowering.py`` documents and recognises."""
+        M = len(vectors)
+        idx = [i * M + j for i in range(M) for j in range(i + 1 if self_interaction else i)]
+        with self.name_scope(name):
+            T = self.op("Pack", list(vectors), name="stack", N=M, axis=1, T=DataType.FLOAT)
+            Z = self.op("BatchMatMulV2", [T, T], name="MatMul", adj_x=False, adj_y=True, T=DataType.FLOAT)
+            flat = self.reshape(Z, [-1, M * M], name="flatten")
+            ax = self.constant("triangle/axis", np.asarray(1, dtype=np.int32))
+            tri = self.op("GatherV2", [flat, self.constant("triangle/indices", np.asarray(idx, dtype=np.int32)), ax],
+                          name="triangle", Tparams=DataType.FLOAT, Tindices=DataType.INT32, Taxis=DataType.INT32, batch_dims=0)
+            return tri if concat_with is None else self.concat([concat_with, tri], 1, name="concat")
+
     def no_op(self, name, control=()) -> str:
         return self.op("NoOp", [], name=name, control=control)
 

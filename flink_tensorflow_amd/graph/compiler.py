@@ -41,7 +41,11 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
      ``generator_lowering.py``);
    * ``MatMul(u, items) → [BiasAdd | Add(item_bias)] → TopKV2`` → one ``retrieve`` step: the score GEMM and the
      top-k selection fused, no score matrix (kernels/retrieve.hip, ``retrieval_lowering.py``);
-   * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch;
+   * ``GatherV2`` lookups + ``Pack → BatchMatMul(T, T, adj_y) → Reshape → GatherV2(triangle) → [ConcatV2]`` (DLRM's
+     dot interaction) → one ``interact`` step that reads ids and embedding rows and writes the top MLP's input row; a
+     lone ``GatherV2(const table, int32 ids)`` → one ``embed`` step (kernels/interact.hip, ``ranking_lowering.py``);
+   * ``MatMul → [BiasAdd] → [Add] → [act]`` → one MFMA GEMM launch (a column-padded first operand is read in place
+     against zero-padded weight rows);
    * ``uint8 feed → Cast → ResizeBilinear → Sub → Div|Mul`` → the fused preprocess kernel
      (bf16 NHWC, channels padded to 8 for the stem conv);
    * ``Mean(axes=[1,2])`` → global-avg-pool; ``MaxPool``/``AvgPool`` → pool kernel;
@@ -54,7 +58,7 @@ This is the MI355X replacement of libtensorflow's session executor for the hot p
    shared by all of the subtask's bucket plans and identical weights are stored once;
 5. **capture**: one hipGraph per (signature, batch size).
 
-The compiler is thirteen modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
+The compiler is fourteen modules: ``plan.py`` (``Val``, ``Step``, ``Chain``, ``CompileError`` and the helpers that
 map a value to its buffer; re-exported here), ``conv_lowering.py`` (the ``ConvLowering`` mixin: Conv2D chains, the
 pure kernel choice ``select_conv_kernel`` and the block-tail post-passes), ``transformer_lowering.py`` (the
 ``TransformerLowering`` mixin: BERT patterns, token packing), ``detection_lowering.py`` (the ``DetectionLowering``
@@ -64,6 +68,7 @@ ops it absorbs), ``deconv_lowering.py`` (the ``DeconvLowering`` mixin: ``Conv2DB
 ``conv3d_lowering.py`` (the ``Conv3DLowering`` mixin: ``Conv3D`` chains, 3-D pools, uint8 clips),
 ``generator_lowering.py`` (the ``GeneratorLowering`` mixin: instance norm, spatial pads, the image output stage),
 ``retrieval_lowering.py`` (the ``RetrievalLowering`` mixin: the score GEMM + top-k of a two-tower model),
+``ranking_lowering.py`` (the ``RankingLowering`` mixin: embedding lookups and DLRM's dot interaction),
 ``plan_memory.py`` (the ``PlanMemory`` mixin: buffer planning, the batch-slice chain),
 ``plan_run.py`` (the ``PlanRunner`` mixin: eager runs, profiling, calibration, capture, replay, the runner's head
 bypass) and this one (construction, pruning, folding, scheduling, the generic and glue lowerings).
@@ -106,6 +111,7 @@ from .ops_nn import same_pads
 from .plan import Chain, CompileError, Step, Val, _coff, _eff_scale, _host, _target, _view
 from .plan_memory import PlanMemory
 from .plan_run import PlanRunner
+from .ranking_lowering import RankingLowering
 from .recurrent_lowering import RecurrentLowering
 from .retrieval_lowering import RetrievalLowering
 from .transformer_lowering import TransformerLowering
@@ -131,7 +137,8 @@ class _ConstSession:
 
 
 class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering, RecurrentLowering, AudioLowering,
-                       DeconvLowering, Conv3DLowering, RetrievalLowering, ConvLowering, PlanMemory, PlanRunner):
+                       DeconvLowering, Conv3DLowering, RetrievalLowering, RankingLowering, ConvLowering, PlanMemory,
+                       PlanRunner):
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
@@ -223,6 +230,7 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
         self._groups = {}
         self._prematch_transformer()  # layer_norm / attention / embedding patterns (BERT graphs)
         self._prematch_detection()  # the box-decode subgraph in front of a CombinedNonMaxSuppression
+        self._prematch_ranking()  # embedding lookups + dot interaction (its nodes but the last are marked fused)
         if self.token_cap is not None:
             self._setup_packing()  # CompileError when the graph cannot run token-packed
         for f in fed:
@@ -236,6 +244,9 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
 
         def ready(n: str, allow_unfused: bool = False) -> bool:
             node = g[n]
+            grp_ready = self._interact_ready(n)  # the last node of an interaction group stands for the group
+            if grp_ready is not None:
+                return grp_ready
             if any(src not in self.vals for src in node.inputs):
                 return False
             return allow_unfused or node.op not in ("Conv2D", "MatMul") or self._residual_ready(node)
@@ -419,6 +430,10 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
                 if v is not None and v.rows is not None:
                     raise CompileError(f"{node.op} {node.name} reads token-packed rows; no packed lowering")
         op = node.op
+        if node.name in self._interact and self._lower_interaction(node):
+            return
+        if op in ("GatherV2", "Gather") and self._lower_embedding(node):
+            return
         if op == "Conv2D":
             return self._lower_conv(node)
         if op == "DepthwiseConv2dNative":
@@ -531,14 +546,19 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
 
     def _lower_unary_act(self, node: Node) -> bool:
         x = self._get(node.inputs[0])
-        if not self._ew_ok(x):
+        # a column-padded GEMM output (a [B, 1] logit in a buffer of 8 columns) runs over the whole buffer
+        padded = x is not None and not x.is_const and bool(x.phys_c) and x.dtype == torch.bfloat16 and len(x.shape) == 2 \
+            and x.rows is None and x.alias_of is None and x.concat_slot is None and x.shape[0] * x.phys_c % 8 == 0
+        if not padded and not self._ew_ok(x):
             return False
         xa = self._as_bf16(x, node.name)
-        out = self._new(x.shape)
+        out = self._new(x.shape, phys_c=x.phys_c if padded else None)
+        if padded:
+            out.buf_shape = x.buf_shape
         act = _ACTS[node.op]
 
         def run(xa=xa, out=out):
-            K.binary(_view(xa), 0.0, "add", act=act, out=out.buf)
+            K.binary(xa.buf if padded else _view(xa), 0.0, "add", act=act, out=out.buf)
 
         self._emit(node.name, "elementwise", run, [xa], [out])
         self.vals[(node.name, 0)] = out
@@ -580,6 +600,14 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
         wt = b.const.float()
         w_nk = wt if node.attr("transpose_b", False) else wt.t()
         N, Kd = w_nk.shape
+        if a.phys_c and not a.is_const and a.dtype == torch.bfloat16 and a.rows is None and a.alias_of is None \
+                and a.concat_slot is None and a.phys_c % 8 == 0 and a.shape[1] == Kd < a.phys_c:
+            # a column-padded producer (the interact step, a GEMM of N % 8 != 0 columns, a unary activation of one):
+            # read in place against zero weight rows, as a conv reads a channel-padded input against zero filter
+            # rows.  The invariant is that the pad columns are finite (zeros, act(0), sigmoid(0)) and the weight
+            # rows are zero.
+            w_nk = torch.nn.functional.pad(w_nk, (0, a.phys_c - Kd))
+            Kd = a.phys_c
         if Kd % 8:
             return self._lower_glue(node)
         last, scale, bias, residual, act, absorbed = self._conv_chain(node)
@@ -936,7 +964,9 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
             out.qscale = self._qscale(node.name)
         # one storage format per buffer: all fp8 at the concat's scale, or all bf16 (an fp8
         # plan's resize or depthwise branch next to fp8 convs is joined by the bf16 copy below)
-        stride_write = (axis == len(shape) - 1 and len(shape) in (4, 5)
+        producers = [[s.kind for s in self.steps if any(o is v for o in s.outputs)] for v in ins]
+        embeds = all(k == ["embed"] for k in producers)  # embedding lookups write slots of any rank
+        stride_write = (axis == len(shape) - 1 and (len(shape) in (4, 5) or embeds)
                         and (fp8 or not any(v.qscale is not None for v in ins))
                         and all(self._concat_writable(v, node.inputs[i][0], node.name) for i, v in enumerate(ins)))
         if stride_write:
@@ -962,7 +992,7 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
         # consumed by nothing but this concat, and not fetched
         prods = [s for s in self.steps if any(o is v for o in s.outputs)]
         if len(prods) != 1 or prods[0].kind not in ("conv", "pool", "conv_fp8", "pool_fp8", "resize", "deconv",
-                                                        "conv3d", "pool3d", "instnorm", "pad") \
+                                                        "conv3d", "pool3d", "instnorm", "pad", "embed") \
                 or v.concat_slot is not None \
                 or (len(prods[0].outputs) != 1 and not prods[0].meta.get("multi_out")):
             return False

@@ -496,6 +496,14 @@ def _gather(ctx, node, params, indices, *axis):
         *params.shape[:a], *indices.shape, *params.shape[a + 1:]),)
 
 
+@register("SparseSegmentSum")
+def _sparse_segment_sum(ctx, node, data, indices, segment_ids):
+    # a multi-hot embedding bag: row s of the result is the sum of data[indices[k]] over segment_ids[k] == s
+    seg = segment_ids.reshape(-1).long()
+    out = torch.zeros((int(seg.max().item()) + 1 if seg.numel() else 0, *data.shape[1:]), dtype=data.dtype, device=data.device)
+    return (out.index_add_(0, seg, data.index_select(0, indices.reshape(-1).long())),)
+
+
 @register("OneHot")
 def _one_hot(ctx, node, idx, depth, on, off):
     d = int(depth.item())

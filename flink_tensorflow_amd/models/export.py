@@ -122,3 +122,19 @@ def graph_def_to_saved_model(export_dir: str, graph_def, signatures: Mapping[str
         asg = b.op("Assign", [f"{name}:0", init], name=f"{name}/Assign", validate_shape=True, use_locking=True)
         b.variables[name] = asg.split(":")[0]
     return export_saved_model(export_dir, b, variables, signatures, tags=tags, overwrite=overwrite)
+
+
+def export_dlrm_saved_model(export_dir: str, **graph_args) -> str:
+    """The DLRM ranking model (``zoo/dlrm.py``) as a TF 1.x SavedModel with its weights as variables
+    (signature ``serving_default``: ``dense``, ``ids`` -> ``probability``); ``graph_args`` are those of
+    ``dlrm_graph_def``."""
+    from .zoo.dlrm import dlrm_graph_def
+
+    gd = dlrm_graph_def(**graph_args)
+    dims = {n.name: [d.size for d in n.attr["shape"].shape.dim] for n in gd.node if n.op == "Placeholder"}
+    width, F = dims["dense"][1], dims["ids"][1]  # from the built graph, not from a copy of its defaults
+    sig = SignatureDef(inputs={"dense": tensor_info("dense:0", "FLOAT", [-1, width]),
+                               "ids": tensor_info("ids:0", "INT32", [-1, F])},
+                       outputs={"probability": tensor_info("probability:0", "FLOAT", [-1, 1])},
+                       method_name="tensorflow/serving/predict")
+    return graph_def_to_saved_model(export_dir, gd, {"serving_default": sig})

@@ -1687,6 +1687,153 @@ def retrieve_topk(q: torch.Tensor, items: torch.Tensor, k: int, bias: torch.Tens
     return out
 
 
+# ------------------------------------------------------------------------------ ranking: embedding gather + dot interaction
+# The envelope of ``kernels/interact.hip``: at most 64 vectors per record (two 32-row MFMA
+# groups), ``D`` a multiple of 16 up to 256 (a lane keeps half a vector in registers), and an
+# output row that fits the wave's LDS row: every pair at or below the diagonal plus 256 columns.
+INTERACT_MAX_VECTORS = 64
+INTERACT_MAX_WORKGROUPS = 4096  # 16 per CU: beyond that a wave takes further records
+
+
+def _interact_mpad(M: int) -> int:
+    return 32 if M <= 32 else 64
+
+
+def dot_interact_eligible(M: int, D: int, W: int) -> bool:
+    """What ``dot_interact`` takes on the GPU: ``M`` vectors of ``D`` elements, ``W`` logical output columns."""
+    mpad = _interact_mpad(M)
+    return 1 <= M <= INTERACT_MAX_VECTORS and D % 16 == 0 and 16 <= D <= 256 and \
+        1 <= W and -(-W // 8) * 8 <= mpad * (mpad + 1) // 2 + 256
+
+
+def dot_interact_lut(M: int, pairs, first_col: int = 0) -> torch.Tensor:
+    """The selection table of ``dot_interact``: int16 ``[Mpad * Mpad]`` (``Mpad`` = 32 or 64),
+    entry ``i * Mpad + j`` = the output column of ``Z[i, j]`` or -1.  ``pairs`` lists ``(i, j)``
+    in output order, the first landing in column ``first_col``.  ``Z`` is symmetric and the kernel
+    computes only ``i >= j``, so a pair above the diagonal is stored at its mirror; two pairs that
+    name the same entry once mirrored are a ``ValueError`` (one entry has one column)."""
+    if not 1 <= M <= INTERACT_MAX_VECTORS:
+        raise ValueError(f"dot_interact_lut: M={M} outside 1..{INTERACT_MAX_VECTORS}")
+    mpad = _interact_mpad(M)
+    lut = torch.full((mpad * mpad,), -1, dtype=torch.int16)
+    for n, (i, j) in enumerate(pairs):
+        i, j = (int(i), int(j)) if i >= j else (int(j), int(i))
+        if not 0 <= j <= i < M:
+            raise ValueError(f"dot_interact_lut: pair {(i, j)} outside {M} vectors")
+        if int(lut[i * mpad + j]) >= 0:
+            raise ValueError(f"dot_interact_lut: pair {(i, j)} is selected twice (Z is symmetric)")
+        lut[i * mpad + j] = first_col + n
+    return lut
+
+
+def dot_interact(table: torch.Tensor, ids: torch.Tensor, meta: torch.Tensor, lut: torch.Tensor, width: int,
+                 dense: torch.Tensor | None = None, copy_dense: bool = False, out: torch.Tensor | None = None,
+                 workgroups: int | None = None):
+    """The input row of a DLRM top MLP.  Per record ``b`` the ``M`` vectors ``T[m]`` are gathered:
+    ``meta`` is int64 ``[3, M]`` = (first table row of the vector's field, its column in ``ids``
+    or -1 for the activation vector, the field's vocabulary size ``V``), so ``T[m] =
+    table[meta[0, m] + ids[b, meta[1, m]]]`` from the bf16 ``table [rows, D]`` or ``dense[b]``
+    (bf16 ``[B, D]``, any row pitch; at most one ``m``).  ``Z = T T^T`` is accumulated in fp32 and
+    the entries ``lut`` selects (``dot_interact_lut``) are rounded to bf16 once into their columns;
+    with ``copy_dense`` columns ``[0, D)`` are a copy of ``dense[b]`` (written last, whether or not
+    ``meta`` packs it).  Returns bf16 ``[B, Wout]``, ``Wout = roundup(width, 8)``; a column that no
+    pair selects, and every column from ``width`` on, is zero.
+
+    An id outside ``[0, V)`` gives a zero vector, never a clamped or wild address (TF's CPU
+    ``GatherV2`` raises there, its GPU kernel returns zeros).  ``out`` is a preallocated bf16
+    ``[B, Wout]`` view with unit column stride and any row pitch (a concat slot): a captured
+    launch passes it.  ``workgroups`` is the grid of 4-wave workgroups, a wave striding over the
+    records (default: a wave per record, ``INTERACT_MAX_WORKGROUPS`` at most)."""
+    if table.dim() != 2 or ids.dim() != 2 or meta.dim() != 2 or meta.shape[0] != 3:
+        raise ValueError(f"dot_interact: table {tuple(table.shape)} / ids {tuple(ids.shape)} / meta {tuple(meta.shape)} "
+                         "are not [rows, D] / [B, F] / [3, M]")
+    (rows, D), (B, F), M, width = table.shape, ids.shape, meta.shape[1], int(width)
+    wout = -(-width // 8) * 8
+    if not dot_interact_eligible(M, D, width) or B < 1:
+        raise ValueError(f"dot_interact: B={B}, M={M}, D={D}, width={width} outside the kernel's envelope "
+                         f"(M <= {INTERACT_MAX_VECTORS}, D % 16 == 0, 16 <= D <= 256, roundup(width, 8) <= Mpad (Mpad + 1) / 2 + 256)")
+    if lut.numel() != _interact_mpad(M) ** 2:
+        raise ValueError(f"dot_interact: lut has {lut.numel()} entries, {_interact_mpad(M) ** 2} needed for M={M}")
+    if dense is not None and (dense.dim() != 2 or tuple(dense.shape) != (B, D) or dense.stride(1) != 1):
+        raise ValueError(f"dot_interact: dense {tuple(dense.shape)} is not a [{B}, {D}] view with unit column stride")
+    if copy_dense and (dense is None or width < D):
+        raise ValueError("dot_interact: copy_dense needs the activation vector and width >= D")
+    if out is not None and (out.dim() != 2 or tuple(out.shape) != (B, wout) or out.stride(1) != 1):
+        raise ValueError(f"dot_interact: out {tuple(out.shape)} is not a [{B}, {wout}] view with unit column stride")
+    if not table.is_cuda:
+        mt = meta.long()
+        T = torch.zeros((B, _interact_mpad(M), D), dtype=torch.float32)  # the LUT indexes the padded Z
+        for m in range(M):
+            base, col, V = (int(v) for v in mt[:, m])
+            if col < 0:
+                T[:, m] = dense.float() if dense is not None else 0.0
+                continue
+            i = ids[:, col].long()
+            ok = (i >= 0) & (i < V) & (base + i >= 0) & (base + i < rows)
+            T[:, m] = torch.where(ok[:, None], table[(base + i).clamp(0, rows - 1)].float(), 0.0)
+        Z = (T @ T.transpose(1, 2)).reshape(B, -1)
+        res = torch.zeros((B, wout), dtype=torch.float32)
+        sel = lut.long()
+        src = torch.nonzero((sel >= 0) & (sel < width)).reshape(-1)
+        res[:, sel[src]] = Z[:, src]
+        if copy_dense:
+            res[:, :D] = dense.float()
+        res = res.to(torch.bfloat16)
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+    dev = table.device
+    _check(table, "table", torch.bfloat16, dev)
+    _check(meta, "meta", torch.int64, dev)
+    _check(lut, "lut", torch.int16, dev)
+    if ids.dtype != torch.int32 or ids.device != dev or ids.stride(1) != 1:
+        raise ValueError("dot_interact: ids must be int32 on the table's device with unit column stride")
+    if dense is not None and (dense.dtype != torch.bfloat16 or dense.device != dev):
+        raise ValueError("dot_interact: dense must be bf16 on the table's device")
+    if out is None:
+        out = torch.empty((B, wout), dtype=torch.bfloat16, device=dev)
+    if out.dtype != torch.bfloat16 or out.device != dev:
+        raise ValueError("dot_interact: out must be bf16 on the table's device")
+    _hip().dot_interact(table.data_ptr(), rows, ids.data_ptr(), ids.stride(0), F, meta.data_ptr(), lut.data_ptr(),
+                        _ptr(dense), dense.stride(0) if dense is not None else 0, int(bool(copy_dense)), B, M, D, width,
+                        out.data_ptr(), out.stride(0),
+                        min(-(-B // 4), INTERACT_MAX_WORKGROUPS) if workgroups is None else int(workgroups), _stream())
+    return out
+
+
+def embed_rows(table: torch.Tensor, ids: torch.Tensor, base: int = 0, vocab: int | None = None,
+               out: torch.Tensor | None = None):
+    """``out[r, :] = table[base + ids[r]]`` as bf16 for the flattened int32 ``ids``: a plain
+    embedding lookup in the field whose ``vocab`` rows start at row ``base`` of the bf16 ``table
+    [rows, D]``, ``D % 8 == 0``.  An id outside ``[0, vocab)`` gives a zero row.  ``out`` is a
+    preallocated bf16 ``[R, D]`` view with unit column stride and any row pitch (a concat slot)."""
+    if table.dim() != 2 or table.shape[1] % 8 or ids.numel() < 1:
+        raise ValueError(f"embed_rows: table {tuple(table.shape)} is not [rows, D] with D % 8 == 0, or no ids")
+    (rows, D), R = table.shape, ids.numel()
+    vocab = rows - base if vocab is None else int(vocab)
+    if out is not None and (out.dim() != 2 or tuple(out.shape) != (R, D) or out.stride(1) != 1):
+        raise ValueError(f"embed_rows: out {tuple(out.shape)} is not a [{R}, {D}] view with unit column stride")
+    if not table.is_cuda:
+        i = ids.reshape(-1).long()
+        ok = (i >= 0) & (i < vocab) & (base + i >= 0) & (base + i < rows)
+        res = torch.where(ok[:, None], table[(base + i).clamp(0, rows - 1)].float(), 0.0).to(torch.bfloat16)
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+    dev = table.device
+    _check(table, "table", torch.bfloat16, dev)
+    _check(ids, "ids", torch.int32, dev)
+    if out is None:
+        out = torch.empty((R, D), dtype=torch.bfloat16, device=dev)
+    if out.dtype != torch.bfloat16 or out.device != dev:
+        raise ValueError("embed_rows: out must be bf16 on the table's device")
+    _hip().embed_rows(table.data_ptr(), rows, ids.data_ptr(), int(base), vocab, R, D, out.data_ptr(), out.stride(0),
+                      _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------ LSTM recurrence
 LSTM_MAX_HIDDEN = 512
 LSTM_RESIDENT_HIDDEN = 128  # up to here the recurrent weights stay in registers for all steps
