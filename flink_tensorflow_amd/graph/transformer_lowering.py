@@ -13,6 +13,17 @@ Google's ``modeling.py``) arrives as decomposed ops.  Before lowering, the compi
   concatenated at compile time) + ONE flash-style ``attention`` launch; the
   ``(1 - mask) * -10000`` adder is replaced by the kernel's key mask (the int32
   ``input_mask``), and its subgraph disappears when nothing else reads it;
+* causal self-attention — the same chain whose adder is ``(1 - M) * c`` with ``M = Mul(A, C)``
+  in either operand order (what ``modeling.py`` builds from a 3-D ``attention_mask``): ``A`` is
+  the key-mask chain above (``Cast`` / ``ExpandDims`` / ``Reshape`` over the fed mask or
+  ``NotEqual(ids, 0)``) and ``C`` a constant with trailing dims ``[S, S]``, every other dim 1,
+  equal to the lower-triangular ones matrix exactly -> the fused QKV ``gemm`` + ONE
+  ``causal_attention`` launch (``kernels/attention_causal.hip``, ``S <= 2048``).  Any other
+  constant (upper or strict lower triangle, a band, a shifted diagonal, values other than 0/1)
+  matches nothing and the ``BatchMatMul`` / ``Softmax`` chain stays glue, as do a causal mask
+  with no key mask and one given as a second adder.  Causal graphs do not token-pack;
+* embeddings without a token-type row (``GatherV2 + positions -> layer_norm``, an item or event
+  embedding) take the same ``embed_layernorm`` launch with a zero type row;
 * GELU — BERT's tanh form after a ``MatMul+BiasAdd`` -> the GEMM's GELU epilogue;
 * ``StridedSlice`` with constant bounds (the pooler's first token) -> one strided device
   copy; ``Squeeze`` / ``ExpandDims`` -> reshape aliases.
@@ -199,41 +210,55 @@ class TransformerLowering:
         if any(b is None for b in br) or len({b[0] for b in br}) != 1:
             return
         # the mask adder: a chain of unary / constant-operand ops over ONE non-constant leaf
-        mask_src, chain = self._mask_leaf(adder_src)
+        mask_src, chain, tril_src = self._mask_leaf(adder_src)
         if mask_src is None:
             return
         members = {add.name, mul.name, bmm1.name, sm.name, bmm2.name, tr_o.name, rs_o.name}
         for _, mm, ba, rs, tr in br:
             members |= {mm.name, ba.name, rs.name, tr.name}
         self._add_group({"kind": "attn", "x": br[0][0], "branches": [b[1:] for b in br], "scale": scale_src,
-                         "mask": mask_src, "mask_chain": chain, "perm": tr_o.inputs[1], "out": rs_o.name,
-                         "members": members})
+                         "mask": mask_src, "mask_chain": chain, "causal": tril_src is not None, "tril": tril_src,
+                         "perm": tr_o.inputs[1], "out": rs_o.name, "members": members})
 
     def _mask_leaf(self, src):
-        """(leaf tensor, chain node names) of ``(1 - Cast(m)[:, None, None, :]) * c`` where
-        ``m`` is a fed int mask (1 = keep) or ``NotEqual(ids, 0)`` of the fed ids — in both
-        cases "key j is padding" is ``leaf[b, j] == 0``, the attention kernel's pad test."""
-        chain, cur = [], self._node(src)
+        """(leaf tensor, chain node names, tril constant or None) of
+        ``(1 - Cast(m)[:, None, None, :]) * c`` where ``m`` is a fed int mask (1 = keep) or
+        ``NotEqual(ids, 0)`` of the fed ids — in both cases "key j is padding" is
+        ``leaf[b, j] == 0``, the attention kernel's pad test.  The causal form has one more link
+        right under the ``Sub``: ``(1 - Mul(A, C)) * c`` (either operand order) with ``A`` the key
+        mask chain above and ``C`` the lower-triangular ones constant (``_is_tril``)."""
+        none = (None, None, None)
+        chain, cur, tril = [], self._node(src), None
         for i in range(7):
             if cur is None:
-                return None, None
+                return none
             if i == 0 and cur.op != "Mul" or i == 1 and cur.op != "Sub":
-                return None, None
+                return none
             if i >= 2 and cur.op not in ("ExpandDims", "Reshape", "Cast", "NotEqual"):
-                return None, None
+                return none
             chain.append(cur.name)
             nonconst = [s for s in cur.inputs if not self._is_const_node(s)]
             if len(nonconst) != 1:
-                return None, None
+                return none
             if cur.op == "NotEqual":
                 c = self._const_of(next(s for s in cur.inputs if s != nonconst[0]))
                 if c is None or c.numel() != 1 or float(c.reshape(-1)[0]) != 0.0:
-                    return None, None
+                    return none
             nxt = self._node(nonconst[0])
             if nxt.op in ("Placeholder", "PlaceholderV2"):
-                return nonconst[0], chain
+                return nonconst[0], chain, tril
+            if i == 1 and nxt.op == "Mul":  # the causal link: M = A * tril
+                a_src = [s for s in nxt.inputs if not self._is_const_node(s)]
+                c_src = [s for s in nxt.inputs if self._is_const_node(s)]
+                if len(a_src) != 1 or len(c_src) != 1 or not _is_tril(self._const_of(c_src[0])):
+                    return none
+                chain.append(nxt.name)
+                tril = c_src[0]
+                nxt = self._node(a_src[0])
+                if nxt.op in ("Placeholder", "PlaceholderV2"):
+                    return a_src[0], chain, tril
             cur = nxt
-        return None, None
+        return none
 
     def _match_embedding(self, ga):
         if len(ga.inputs) < 2 or not self._is_const_node(ga.inputs[0]) or self._is_const_node(ga.inputs[1]):
@@ -241,12 +266,16 @@ class TransformerLowering:
         if len(ga.inputs) > 2 and not self._is_const_node(ga.inputs[2]):
             return
         a0 = self._only_consumer(ga.name, _ADDS)
-        a1 = self._only_consumer(a0.name, _ADDS) if a0 is not None else None
-        if a1 is None:
+        if a0 is None:
             return
         pos_src = next(s for s in a0.inputs if s[0] != ga.name)
-        typ_src = next(s for s in a1.inputs if s[0] != a0.name)
-        if not (self._is_const_node(pos_src) and self._is_const_node(typ_src)):
+        ln0 = next((g for g in self._groups.values() if g["kind"] == "ln" and g["x"] == (a0.name, 0)), None)
+        # no token-type row (an item / event embedding): the LayerNorm reads ``gather + positions``
+        a1 = a0 if ln0 is not None else self._only_consumer(a0.name, _ADDS)
+        if a1 is None:
+            return
+        typ_src = None if a1 is a0 else next(s for s in a1.inputs if s[0] != a0.name)
+        if not (self._is_const_node(pos_src) and (typ_src is None or self._is_const_node(typ_src))):
             return
         ln = next((g for g in self._groups.values() if g["kind"] == "ln" and g["x"] == (a1.name, 0)), None)
         if ln is None or not set(self._consumers(a1.name)) <= ln["members"]:
@@ -288,6 +317,8 @@ class TransformerLowering:
         attns = [g for g in grps if g["kind"] == "attn"]
         if len(embs) != 1 or not attns:
             raise CompileError("token packing needs one embedding group and fused attention")
+        if any(g.get("causal") for g in attns):
+            raise CompileError("token packing does not cover causal attention (no packed causal kernel)")
         ids_src = embs[0]["ids"]
         feed = f"{ids_src[0]}:{ids_src[1]}"  # feed names are normalised to ``node:index``
         if feed not in self.feed_names:
@@ -449,7 +480,10 @@ class TransformerLowering:
 
     def _lower_emb_group(self, grp) -> bool:
         ids = self._get(grp["ids"])
-        word, pos, typ = (self._const_of(grp[k]) for k in ("word", "pos", "type"))
+        word, pos = (self._const_of(grp[k]) for k in ("word", "pos"))
+        typ = self._const_of(grp["type"]) if grp["type"] is not None else None
+        if grp["type"] is None and word is not None:
+            typ = torch.zeros(1, word.shape[-1])  # no token-type row in the graph
         p = self._ln_params(grp["ln"])
         if ids is None or ids.is_const or word is None or pos is None or typ is None or p is None:
             return False
@@ -544,6 +578,10 @@ class TransformerLowering:
         if dh != 64 or (pk is None and B * S != T) or tuple(mask.shape) != (B, S) or \
                 any(w.shape != (H, Din) for w in ws):
             return False
+        causal = grp.get("causal", False)
+        if causal and (pk is not None or S > K.CAUSAL_ATTENTION_MAX_SEQ
+                       or not _is_tril(self._const_of(grp["tril"]), S)):  # the folded constant, checked again
+            return False
         w_qkv = self._dev(torch.cat(ws, 0), torch.bfloat16)
         b_qkv = self._dev(torch.cat(bs, 0), torch.float32)
         self.params += [w_qkv, b_qkv]
@@ -577,10 +615,12 @@ class TransformerLowering:
             mask = cu
         else:
             def run_attn(qkv=qkv, ctx=ctx, mask=mask):
-                K.attention(qkv.buf, _view(mask).reshape(-1), B, S, nh, pad_id=0, scale=sc, out=ctx.buf)
+                K.attention(qkv.buf, _view(mask).reshape(-1), B, S, nh, pad_id=0, scale=sc, out=ctx.buf,
+                            causal=causal)
 
+        kind = "cls_attention" if cls_only else "causal_attention" if causal else "attention"
         self._emit(grp["out"] + "/qkv", "gemm", run_qkv, [xin], [qkv], {"impl": "gemm_pp", "fused": "qkv"})
-        self._emit(grp["out"], "cls_attention" if cls_only else "attention", run_attn, [qkv, mask], [ctx])
+        self._emit(grp["out"], kind, run_attn, [qkv, mask], [ctx])
         self.vals[(grp["out"], 0)] = ctx
         return True
 
@@ -694,3 +734,12 @@ class TransformerLowering:
 
 def _rows(v, D):
     return _view(v).reshape(-1, D)
+
+
+def _is_tril(c, S: int | None = None) -> bool:
+    """``c`` is the causal constant: trailing dims ``[S, S]``, every other dim 1, and exactly the
+    lower-triangular ones matrix (1 where key <= query, 0 elsewhere)."""
+    if c is None or c.dim() < 2 or c.shape[-1] != c.shape[-2] or c.numel() != c.shape[-1] ** 2:
+        return False
+    n = c.shape[-1]
+    return (S is None or n == S) and torch.equal(c.reshape(n, n).double(), torch.ones(n, n, dtype=torch.float64).tril())

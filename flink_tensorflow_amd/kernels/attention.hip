@@ -19,23 +19,12 @@
 
 #include <stdexcept>
 
+#include "attention_tiles.h"
 #include "common.h"
 
 namespace {
 
-constexpr int D = 64;      // head dim
-constexpr int VP = D + 8;  // V row pitch (elements): tr-read rows land on distinct banks
-constexpr int OP = D + 8;   // output staging row pitch
-constexpr int QP = 16 + 4;  // P^T row pitch: [key][16 q] tiles, 40-B rows (tr-read friendly)
-
-typedef short v4s __attribute__((ext_vector_type(4)));
-
-FTM_DEVICE int kswz(int row, int chunk) { return row * D + ((chunk ^ (row & 7)) << 3); }
-
-// 4 consecutive keys x 1 d column per lane (a 16-lane group reads 4 keys x 16 d columns)
-FTM_DEVICE v4s tr_read(const bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)p);
-}
+using namespace attn;  // D, VP, OP, QP, kswz, tr_read: shared with attention_causal.hip
 
 // QB queries x KB keys per step (KB = 128 covers BERT's S <= 128 in ONE staging round:
 // no second K/V round trip and no online-softmax rescale)

@@ -138,3 +138,19 @@ def export_dlrm_saved_model(export_dir: str, **graph_args) -> str:
                        outputs={"probability": tensor_info("probability:0", "FLOAT", [-1, 1])},
                        method_name="tensorflow/serving/predict")
     return graph_def_to_saved_model(export_dir, gd, {"serving_default": sig})
+
+
+def export_next_item_saved_model(export_dir: str, cfg=None, seq_len: int = 64, k: int = 10, **graph_args) -> str:
+    """The next-item recommender (``zoo/next_item.py``) as a TF 1.x SavedModel with its weights as
+    variables (signature ``serving_default``: ``item_ids`` -> ``scores``, ``items``); ``graph_args`` are
+    the remaining ones of ``next_item_graph_def``."""
+    from .zoo.next_item import NextItemConfig, next_item_graph_def
+
+    cfg = cfg or NextItemConfig()
+    gd = next_item_graph_def(cfg, seq_len, k, **graph_args)
+    k = min(k, cfg.num_items)
+    sig = SignatureDef(inputs={"item_ids": tensor_info("item_ids:0", "INT32", [-1, seq_len])},
+                       outputs={"scores": tensor_info("top_k:0", "FLOAT", [-1, k]),
+                                "items": tensor_info("top_k:1", "INT32", [-1, k])},
+                       method_name="tensorflow/serving/predict")
+    return graph_def_to_saved_model(export_dir, gd, {"serving_default": sig})

@@ -11,7 +11,8 @@ _EXPORTS = {"MobileNetV1Model": "image_classifier", "mobilenet_v1_graph_def": "m
             "export_style_transfer_saved_model": "style_transfer",
             "RetrievalModel": "two_tower", "two_tower_graph_def": "two_tower",
             "export_two_tower_saved_model": "two_tower",
-            "DLRMModel": "dlrm", "dlrm_graph_def": "dlrm", "export_dlrm_saved_model": "dlrm"}
+            "DLRMModel": "dlrm", "dlrm_graph_def": "dlrm", "export_dlrm_saved_model": "dlrm",
+            "NextItemModel": "next_item", "NextItemConfig": "next_item", "next_item_graph_def": "next_item"}
 
 __all__ = sorted(_EXPORTS)
 

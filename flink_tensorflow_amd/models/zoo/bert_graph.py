@@ -72,6 +72,52 @@ def gelu(b: GraphBuilder, x: str, scope: str) -> str:
         return b.mul(x, cdf, name="mul_3")
 
 
+def encoder_layers(b: GraphBuilder, W, x2: str, adder: str, S: int, H: int, nh: int, layers: int, eps: float,
+                   scope: str = "bert/encoder/") -> str:
+    """``layers`` post-LN transformer blocks over ``x2`` [B*S, H] as ``modeling.py`` emits them
+    (``adder`` is the additive attention mask, ``W(name)`` the weight constant of a variable) ->
+    the last block's output [B*S, H]."""
+    dh = H // nh
+    shp4 = [-1, S, nh, dh]
+    perm = _c(b, scope + "perm", np.asarray([0, 2, 1, 3], np.int32))
+    for l in range(layers):
+        p = f"{scope}layer_{l}/"
+
+        def dense(t, nm, k_name, act_scope=None):
+            y = b.bias_add(b.matmul(t, W(p + k_name + "/kernel"), name=p + k_name + "/MatMul"),
+                           W(p + k_name + "/bias"), name=p + k_name + "/BiasAdd")
+            return y
+
+        heads = []
+        for nm in ("query", "key", "value"):
+            t = dense(x2, nm, f"attention/self/{nm}")
+            t = b.reshape(t, shp4, name=p + f"attention/self/Reshape_{nm}")
+            heads.append(b.op("Transpose", [t, perm], name=p + f"attention/self/transpose_{nm}", T=DataType.FLOAT,
+                              Tperm=DataType.INT32))
+        q, k, v = heads
+        sc = b.op("BatchMatMulV2", [q, k], name=p + "attention/self/MatMul", T=DataType.FLOAT, adj_x=False,
+                  adj_y=True)
+        sc = b.mul(sc, _c(b, p + "attention/self/Mul/y", np.float32(1.0 / math.sqrt(dh))),
+                   name=p + "attention/self/Mul")
+        sc = b.add(sc, adder, name=p + "attention/self/add")
+        pr = b.softmax(sc, name=p + "attention/self/Softmax")
+        ctx = b.op("BatchMatMulV2", [pr, v], name=p + "attention/self/MatMul_1", T=DataType.FLOAT, adj_x=False,
+                   adj_y=False)
+        ctx = b.op("Transpose", [ctx, perm], name=p + "attention/self/transpose_3", T=DataType.FLOAT,
+                   Tperm=DataType.INT32)
+        ctx = b.reshape(ctx, [-1, H], name=p + "attention/self/Reshape_3")
+        o = dense(ctx, "o", "attention/output/dense")
+        o = b.add(o, x2, name=p + "attention/output/add")
+        x2 = layer_norm(b, o, W(p + "attention/output/LayerNorm/gamma"), W(p + "attention/output/LayerNorm/beta"),
+                        eps, p + "attention/output/LayerNorm")
+        f = gelu(b, dense(x2, "i", "intermediate/dense"), p + "intermediate/dense/gelu")
+        f = dense(f, "f", "output/dense")
+        f = b.add(f, x2, name=p + "output/add")
+        x2 = layer_norm(b, f, W(p + "output/LayerNorm/gamma"), W(p + "output/LayerNorm/beta"), eps,
+                        p + "output/LayerNorm")
+    return x2
+
+
 def bert_graph_def(cfg: BertConfig, seq_len: int, weights: dict | None = None, seed: int = 0,
                    mask_from_ids: bool = False) -> tuple[GraphDef, dict]:
     """(GraphDef, weights) for a BERT sequence classifier on [B, seq_len] inputs (B dynamic).
@@ -83,7 +129,6 @@ def bert_graph_def(cfg: BertConfig, seq_len: int, weights: dict | None = None, s
     (frozen graph) — ``export_bert_saved_model`` turns them into variables."""
     w = weights if weights is not None else init_bert_weights(cfg, seed)
     H, S, nh = cfg.hidden, seq_len, cfg.heads
-    dh = H // nh
     b = GraphBuilder()
 
     def W(name):
@@ -130,43 +175,7 @@ def bert_graph_def(cfg: BertConfig, seq_len: int, weights: dict | None = None, s
     one_minus = b.sub(_c(b, "bert/encoder/sub/x", np.float32(1.0)), m4, name="bert/encoder/sub")
     adder = b.mul(one_minus, _c(b, "bert/encoder/mul/y", np.float32(-10000.0)), name="bert/encoder/mul")
     x2 = b.reshape(x, [-1, H], name="bert/encoder/Reshape")
-    shp4 = [-1, S, nh, dh]
-    perm = _c(b, "bert/encoder/perm", np.asarray([0, 2, 1, 3], np.int32))
-    for l in range(cfg.layers):
-        p = f"bert/encoder/layer_{l}/"
-
-        def dense(t, nm, k_name, act_scope=None):
-            y = b.bias_add(b.matmul(t, W(p + k_name + "/kernel"), name=p + k_name + "/MatMul"),
-                           W(p + k_name + "/bias"), name=p + k_name + "/BiasAdd")
-            return y
-
-        heads = []
-        for nm in ("query", "key", "value"):
-            t = dense(x2, nm, f"attention/self/{nm}")
-            t = b.reshape(t, shp4, name=p + f"attention/self/Reshape_{nm}")
-            heads.append(b.op("Transpose", [t, perm], name=p + f"attention/self/transpose_{nm}", T=DataType.FLOAT,
-                              Tperm=DataType.INT32))
-        q, k, v = heads
-        sc = b.op("BatchMatMulV2", [q, k], name=p + "attention/self/MatMul", T=DataType.FLOAT, adj_x=False,
-                  adj_y=True)
-        sc = b.mul(sc, _c(b, p + "attention/self/Mul/y", np.float32(1.0 / math.sqrt(dh))),
-                   name=p + "attention/self/Mul")
-        sc = b.add(sc, adder, name=p + "attention/self/add")
-        pr = b.softmax(sc, name=p + "attention/self/Softmax")
-        ctx = b.op("BatchMatMulV2", [pr, v], name=p + "attention/self/MatMul_1", T=DataType.FLOAT, adj_x=False,
-                   adj_y=False)
-        ctx = b.op("Transpose", [ctx, perm], name=p + "attention/self/transpose_3", T=DataType.FLOAT,
-                   Tperm=DataType.INT32)
-        ctx = b.reshape(ctx, [-1, H], name=p + "attention/self/Reshape_3")
-        o = dense(ctx, "o", "attention/output/dense")
-        o = b.add(o, x2, name=p + "attention/output/add")
-        x2 = layer_norm(b, o, W(p + "attention/output/LayerNorm/gamma"), W(p + "attention/output/LayerNorm/beta"),
-                        cfg.eps, p + "attention/output/LayerNorm")
-        f = gelu(b, dense(x2, "i", "intermediate/dense"), p + "intermediate/dense/gelu")
-        f = dense(f, "f", "output/dense")
-        f = b.add(f, x2, name=p + "output/add")
-        x2 = layer_norm(b, f, W(p + "output/LayerNorm/gamma"), W(p + "output/LayerNorm/beta"), cfg.eps,
-                        p + "output/LayerNorm")
+    x2 = encoder_layers(b, W, x2, adder, S, H, nh, cfg.layers, cfg.eps)
     seq = b.reshape(x2, [-1, S, H], name="bert/encoder/Reshape_out")
     first = b.op("StridedSlice", [seq, _c(b, "bert/pooler/strided_slice/stack", np.asarray([0, 0, 0], np.int32)),
                                   _c(b, "bert/pooler/strided_slice/stack_1", np.asarray([0, 1, 0], np.int32)),

@@ -2246,16 +2246,25 @@ def softmax_topk(logits: torch.Tensor, k: int, want_probs: bool = False, vals=No
 
 
 # ------------------------------------------------------------------------------ attention
+CAUSAL_ATTENTION_MAX_SEQ = 2048  # longest sequence of the causal attention kernel
+
+
 def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int, heads: int, pad_id: int = 0,
               scale: float | None = None, out: torch.Tensor | None = None,
-              cu_seqlens: torch.Tensor | None = None) -> torch.Tensor:
+              cu_seqlens: torch.Tensor | None = None, causal: bool = False) -> torch.Tensor:
     """Multi-head self-attention over the fused QKV projection output.
 
     Padded batch: ``qkv`` [B*S, 3*H*64] bf16 (Q|K|V blocks, head h at h*64), ``ids`` [B*S]
     int32 token ids (keys whose id == ``pad_id`` are masked).  Packed batch
     (``cu_seqlens`` [B+1] int32 given, ``seq`` = the longest sequence): sequence b is rows
     ``cu[b]:cu[b+1]`` of ``qkv``, no padding; rows past ``cu[B]`` are left untouched.
-    Returns ctx [rows, H*64]."""
+    ``causal`` (padded batch only, ``1 <= S <= 2048``): query i attends key j iff ``j <= i`` and key
+    j is not padding, on ``kernels/attention_causal.hip``; a query with no admissible key gets a
+    zero row.  Returns ctx [rows, H*64]."""
+    if causal and cu_seqlens is not None:
+        raise ValueError("attention: causal attention of a packed batch (cu_seqlens) is not supported")
+    if causal and not 1 <= seq <= CAUSAL_ATTENTION_MAX_SEQ:  # the kernel's envelope, on the host path too
+        raise ValueError(f"attention: causal attention needs 1 <= seq <= {CAUSAL_ATTENTION_MAX_SEQ}, got {seq}")
     T = qkv.shape[0] if cu_seqlens is not None else batch * seq
     Dh = qkv.shape[1] // (3 * heads)
     if qkv.shape != (T, 3 * heads * Dh):
@@ -2274,6 +2283,10 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
             _check(cu_seqlens, "cu_seqlens", torch.int32, qkv.device)
         else:
             _check(ids, "ids", torch.int32, qkv.device)
+        if causal:
+            _hip().attention_causal_fwd_bf16(qkv.data_ptr(), ids.data_ptr(), out.data_ptr(), batch, seq, heads, Dh,
+                                             pad_id, float(scale), _stream())
+            return out
         _hip().attention_fwd_bf16(qkv.data_ptr(), _ptr(ids) if cu_seqlens is None else 0, _ptr(cu_seqlens),
                                   out.data_ptr(), batch, seq, heads, Dh, pad_id, float(scale), _stream())
         return out
@@ -2289,6 +2302,8 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
     q, k, v = qkv.float().reshape(batch, seq, 3, heads, Dh).permute(2, 0, 3, 1, 4)
     s = (q @ k.transpose(-1, -2)) * scale
     mask = (ids.reshape(batch, 1, 1, seq) == pad_id)
+    if causal:  # key j > query i
+        mask = mask | torch.ones(seq, seq, dtype=torch.bool, device=ids.device).triu(1)
     s = s.masked_fill(mask, float("-inf"))
     p = torch.softmax(s, -1).nan_to_num(0.0)
     o = (p @ v).permute(0, 2, 1, 3).reshape(T, heads * Dh)
