@@ -10,7 +10,8 @@ Google's ``modeling.py``) arrives as decomposed ops.  Before lowering, the compi
 * self-attention — the query/key/value ``MatMul+BiasAdd -> Reshape -> Transpose`` of one
   input, ``BatchMatMul(adj_y) -> Mul(scale) -> Add(mask adder) -> Softmax -> BatchMatMul
   -> Transpose -> Reshape`` -> ONE fused QKV projection on the ping-pong MFMA GEMM (weights
-  concatenated at compile time) + ONE flash-style ``attention`` launch; the
+  concatenated at compile time) + ONE flash-style ``attention`` launch, for heads 32, 64 or 128
+  wide (``ops.kernels.ATTENTION_HEAD_DIMS``; any other width leaves the chain unmatched); the
   ``(1 - mask) * -10000`` adder is replaced by the kernel's key mask (the int32
   ``input_mask``), and its subgraph disappears when nothing else reads it;
 * causal self-attention — the same chain whose adder is ``(1 - M) * c`` with ``M = Mul(A, C)``
@@ -575,7 +576,7 @@ class TransformerLowering:
         B = pk["B"] if pk is not None else T // S
         if pk is not None and (S != pk["S"] or pk["cu"] is None):
             return False
-        if dh != 64 or (pk is None and B * S != T) or tuple(mask.shape) != (B, S) or \
+        if dh not in K.ATTENTION_HEAD_DIMS or (pk is None and B * S != T) or tuple(mask.shape) != (B, S) or \
                 any(w.shape != (H, Din) for w in ws):
             return False
         causal = grp.get("causal", False)

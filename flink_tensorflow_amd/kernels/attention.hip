@@ -17,6 +17,7 @@
 // __shfl_xor; the normalised O tile is staged through LDS and stored as whole 128-B rows.
 #include <pybind11/pybind11.h>
 
+#include <climits>
 #include <stdexcept>
 
 #include "attention_tiles.h"
@@ -201,6 +202,97 @@ __global__ __launch_bounds__(QB * 4) void attention_fwd_kernel(const bf16* __res
   }
 }
 
+// Head dims 32 and 128 (tile<DH>, key_step and store_ctx of attention_tiles.h).  One workgroup =
+// one (batch, head GROUP, query block) of NW waves:
+//   DH = 32:  the group is the head pair (2p, 2p+1); wave w is head w & 1 of the pair and query
+//             group w >> 1, so NW = 8 waves cover 64 queries x 2 heads.  K/V staging and the ctx
+//             store move the pair's whole 128-B rows, S is one MFMA per key fragment, O is two
+//             accumulator fragments per wave, and the LDS footprint (KB = 128: 16 + 18 + 40 KB)
+//             and the wave count are those of the 64-wide <128, 128> kernel: two workgroups per CU.
+//             With an odd H the last pair has one head: its second half-row is neither loaded
+//             (zeros are staged) nor stored, and the waves of the absent head run on zeros.
+//   DH = 128: one head, 256-B rows, four K-steps per key fragment, eight O fragments (32
+//             accumulator registers) per wave.  KB = 64: K 16 KB + V 18 KB + 8 P/O slots of
+//             4.25 KB = 68.5 KB, two workgroups (16 waves) per CU; KB = 128 would take 110 KB and
+//             leave one.  The P slot is sized by the O staging tile (16 x 136) here, not by KB.
+template <int DH, int NW, int KB>
+__global__ __launch_bounds__(NW * 64) void attention_fwd_hd_kernel(const bf16* __restrict__ qkv,
+                                                                   const int* __restrict__ ids,
+                                                                   const int* __restrict__ cu, bf16* __restrict__ out,
+                                                                   int B, int S, int H, int pad_id,
+                                                                   float scale_log2e) {
+  using T = tile<DH>;
+  constexpr int HP = T::HP, NCH = T::NCH;
+  constexpr int QB = NW * 16 / HP;  // queries per workgroup
+  constexpr int NTH = NW * 64;
+  constexpr int PSLOT = T::pslot(KB);
+  __shared__ __attribute__((aligned(16))) bf16 Ks[KB * T::RW];  // [key][group row] swizzled
+  __shared__ __attribute__((aligned(16))) bf16 Vs[KB * T::VP];  // [key][group row] (+pad)
+  __shared__ __attribute__((aligned(16))) bf16 Ps[NW * PSLOT];  // per-wave P^T, reused for O staging
+  __shared__ float kmask[KB];
+
+  const int qblocks = (S + QB - 1) / QB;
+  const int HG = (H + HP - 1) / HP;  // head groups
+  const int bg = blockIdx.x / qblocks;
+  const int qb = blockIdx.x % qblocks;
+  const int b = bg / HG, h0 = (bg % HG) * HP;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hp = wave % HP, qg = wave / HP;
+  const int HD = H * DH, ld = 3 * HD;
+  const int vch = min(HP, H - h0) * (DH / 8);  // 16-B chunks of the group row that exist
+  const size_t tok0 = cu ? (size_t)cu[b] : (size_t)b * S;
+  const int Sb = cu ? cu[b + 1] - cu[b] : S;
+  if (qb * QB >= Sb) return;  // block-uniform: this query block lies past the sequence
+
+  const int qrow = qb * QB + qg * 16 + (lane & 15);
+  bf16x8 qa[T::NKS];
+#pragma unroll
+  for (int ks = 0; ks < T::NKS; ++ks) {
+    if (qrow < Sb && h0 + hp < H)
+      qa[ks] = *reinterpret_cast<const bf16x8*>(qkv + (tok0 + qrow) * ld + (h0 + hp) * DH + ks * 32 + (lane >> 4) * 8);
+    else
+      qa[ks] = bf16x8{};
+  }
+  f32x4 o[T::NO];
+#pragma unroll
+  for (int n = 0; n < T::NO; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float mrow[4], lrow[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    mrow[r] = -INFINITY;
+    lrow[r] = 0.f;
+  }
+
+  const bf16* kbase = qkv + tok0 * ld + HD + h0 * DH;  // K of key 0, group row; V lies HD further
+  const int nkb = (Sb + KB - 1) / KB;
+  for (int kb = 0; kb < nkb; ++kb) {
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < KB * NCH / NTH; ++it) {
+      const int q = tid + it * NTH;
+      const int key = q / NCH, ch = q % NCH;
+      const int kg = kb * KB + key;
+      u32x4 kv = {0u, 0u, 0u, 0u}, vv = {0u, 0u, 0u, 0u};
+      if (kg < Sb && ch < vch) {
+        const bf16* row = kbase + (size_t)kg * ld + ch * 8;
+        kv = *reinterpret_cast<const u32x4*>(row);
+        vv = *reinterpret_cast<const u32x4*>(row + HD);
+      }
+      *reinterpret_cast<u32x4*>(Ks + T::kswz(key, ch)) = kv;
+      *reinterpret_cast<u32x4*>(Vs + key * T::VP + ch * 8) = vv;
+    }
+    if (tid < KB) {
+      const int kg = kb * KB + tid;
+      kmask[tid] = (kg < Sb && (cu || ids[tok0 + kg] != pad_id)) ? 0.f : -INFINITY;
+    }
+    __syncthreads();
+    key_step<DH, KB / 16, false>(Ks, Vs, kmask, Ps + wave * PSLOT, qa, o, mrow, lrow, lane, hp, scale_log2e);
+  }
+  store_ctx<DH>(Ps + (wave - hp) * PSLOT, o, lrow, out + tok0 * HD + h0 * DH, HD, qb * QB + qg * 16, Sb, vch, lane,
+                hp);
+}
+
 // x[t] = LN(word[ids[t]] + pos[t % S] + type[tt[t]]) * gamma + beta   (D % 8 == 0, D <= 2048)
 template <int MAXV>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ ids, const int* __restrict__ tt,
@@ -368,6 +460,79 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restri
   out[(size_t)b * H * D + h * D + lane] = f2bf(n > 0 ? acc / sum : 0.f);
 }
 
+// The same for head dims 32 and 128, still one wave per (sequence, head) and at most 512 keys.  q
+// stays in registers as the DH / 8 packed 16-B vectors it was loaded as (at 128, 128 fp32 copies
+// would cost 128 VGPRs for nothing: widening bf16 is one shift).  PV:
+//   DH = 128: a V row is 256 B; lane l owns columns 2l, 2l + 1 (one 4-B load per key).
+//   DH = 32:  a V row is 64 B, 32 lanes wide.  The wave is not given a second head (its score row
+//             and softmax would double); instead the idle half takes every second key: lane l
+//             owns column l & 31 over the keys of parity l >> 5, and one __shfl_xor(32) adds the
+//             two partial sums, so all 64 lanes load on every step.
+template <int DH>
+__global__ __launch_bounds__(256) void cls_attention_hd_kernel(const bf16* __restrict__ qkv,
+                                                               const int* __restrict__ cu, bf16* __restrict__ out,
+                                                               int B, int H, float scale_log2e) {
+  static_assert(DH == 32 || DH == 128, "64 is cls_attention_kernel");
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  __shared__ float probs[4][512];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int bh = blockIdx.x * 4 + wave;
+  if (bh >= B * H) return;  // wave-uniform; no block barrier below
+  const int b = bh / H, h = bh % H;
+  const int HD = H * DH, ld = 3 * HD;
+  const int t0 = cu[b];
+  const int n = min(cu[b + 1] - t0, 512);
+  bf16* orow = out + (size_t)b * HD + h * DH;
+  const bf16* qrow = qkv + (size_t)t0 * ld + h * DH;
+  float mx = -INFINITY, sum = 0.f;
+  if (n > 0) {  // an empty sequence reads nothing (row t0 may lie one past the batch)
+    bf16x8 qv[DH / 8];
+#pragma unroll
+    for (int c = 0; c < DH / 8; ++c) qv[c] = *reinterpret_cast<const bf16x8*>(qrow + c * 8);
+    for (int j = lane; j < n; j += 64) {
+      const bf16* krow = qrow + (size_t)j * ld + HD;
+      float sdot = 0.f;
+#pragma unroll
+      for (int c = 0; c < DH / 8; ++c) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(krow + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sdot += (float)qv[c][e] * (float)v[e];
+      }
+      sdot *= scale_log2e;
+      probs[wave][j] = sdot;
+      mx = fmaxf(mx, sdot);
+    }
+    mx = wave_reduce_max(mx);
+    for (int j = lane; j < n; j += 64) {
+      const float p = __builtin_amdgcn_exp2f(probs[wave][j] - mx);
+      probs[wave][j] = p;
+      sum += p;
+    }
+    sum = wave_reduce_sum(sum);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's probabilities are in LDS
+  const float inv = n > 0 ? 1.f / sum : 0.f;
+  const bf16* vbase = qrow + 2 * HD;
+  if constexpr (DH == 128) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int j = 0; j < n; ++j) {
+      const bf16x2 v = *reinterpret_cast<const bf16x2*>(vbase + (size_t)j * ld + 2 * lane);
+      a0 += probs[wave][j] * (float)v[0];
+      a1 += probs[wave][j] * (float)v[1];
+    }
+    bf16x2 r;
+    r[0] = f2bf(a0 * inv);
+    r[1] = f2bf(a1 * inv);
+    *reinterpret_cast<bf16x2*>(orow + 2 * lane) = r;
+  } else {
+    float acc = 0.f;
+    for (int j = lane >> 5; j < n; j += 2) acc += probs[wave][j] * (float)vbase[(size_t)j * ld + (lane & 31)];
+    acc += __shfl_xor(acc, 32, 64);
+    if (lane < 32) orow[lane] = f2bf(acc * inv);
+  }
+}
+
 }  // namespace
 
 void pack_tokens(uintptr_t ids, int B, int S, int pad_id, int T_cap, uintptr_t packed, uintptr_t pos, uintptr_t cu,
@@ -381,8 +546,9 @@ void pack_tokens(uintptr_t ids, int B, int S, int pad_id, int T_cap, uintptr_t p
 
 void attention_fwd_bf16(uintptr_t qkv, uintptr_t ids, uintptr_t cu_seqlens, uintptr_t out, int B, int S, int H,
                         int Dh, int pad_id, float scale, uintptr_t stream) {
-  if (Dh != D) throw std::invalid_argument("attention_fwd: head dim must be 64");
+  if (Dh != 32 && Dh != 64 && Dh != 128) throw std::invalid_argument("attention_fwd: head dim must be 32, 64 or 128");
   if (B <= 0 || S <= 0 || H <= 0) throw std::invalid_argument("attention_fwd: empty problem");
+  // rows are H * Dh * 2 bytes, a multiple of 16 for every width, so 16-B chunks need only aligned bases
   if (qkv % 16 || out % 16) throw std::invalid_argument("attention_fwd: pointers must be 16-byte aligned");
   const float kLog2e = 1.4426950408889634f;
   auto st = reinterpret_cast<hipStream_t>(stream);
@@ -391,7 +557,27 @@ void attention_fwd_bf16(uintptr_t qkv, uintptr_t ids, uintptr_t cu_seqlens, uint
   auto CU = reinterpret_cast<const int*>(cu_seqlens);
   if (!I && !CU) throw std::invalid_argument("attention_fwd: need token ids (padded) or cu_seqlens (packed)");
   auto O = reinterpret_cast<bf16*>(out);
-  if (S > 64) {  // 128-query blocks: K/V of a head staged once for S <= 128
+  const long long HG = Dh == 32 ? (H + 1) / 2 : H;  // head groups: pairs at 32
+  auto blocks = [&](int QB) {
+    const long long g = (long long)B * HG * ((S + QB - 1) / QB);
+    if (g > INT_MAX) throw std::invalid_argument("attention_fwd: grid too large");
+    return dim3((unsigned)g);
+  };
+  if (Dh == 32) {  // 8 waves = 64 queries x 2 heads, one staging round for S <= 128; 4 waves for short S
+    if (S > 64)
+      hipLaunchKernelGGL((attention_fwd_hd_kernel<32, 8, 128>), blocks(64), dim3(512), 0, st, Q, I, CU, O, B, S, H,
+                         pad_id, scale * kLog2e);
+    else
+      hipLaunchKernelGGL((attention_fwd_hd_kernel<32, 4, 64>), blocks(32), dim3(256), 0, st, Q, I, CU, O, B, S, H,
+                         pad_id, scale * kLog2e);
+  } else if (Dh == 128) {
+    if (S > 64)
+      hipLaunchKernelGGL((attention_fwd_hd_kernel<128, 8, 64>), blocks(128), dim3(512), 0, st, Q, I, CU, O, B, S, H,
+                         pad_id, scale * kLog2e);
+    else
+      hipLaunchKernelGGL((attention_fwd_hd_kernel<128, 4, 64>), blocks(64), dim3(256), 0, st, Q, I, CU, O, B, S, H,
+                         pad_id, scale * kLog2e);
+  } else if (S > 64) {  // 128-query blocks: K/V of a head staged once for S <= 128
     const int qblocks = (S + 127) / 128;
     hipLaunchKernelGGL((attention_fwd_kernel<128, 128>), dim3(B * H * qblocks), dim3(512), 0, st, Q, I, CU, O, B, S,
                        H, pad_id, scale * kLog2e);
@@ -426,11 +612,14 @@ void embed_ln_bf16(uintptr_t ids, uintptr_t tt, uintptr_t pos_ids, uintptr_t wor
 
 void cls_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale,
                         uintptr_t stream) {
-  if (Dh != D) throw std::invalid_argument("cls_attention: head dim must be 64");
+  if (Dh != 32 && Dh != 64 && Dh != 128) throw std::invalid_argument("cls_attention: head dim must be 32, 64 or 128");
   if (B <= 0 || H <= 0 || !cu) throw std::invalid_argument("cls_attention: empty problem / no cu_seqlens");
-  if (qkv % 16 || out % 2) throw std::invalid_argument("cls_attention: misaligned pointers");
+  // 16-B loads of q and k; the output row is stored 2 B per lane (4 B at 128: two columns a lane)
+  if (qkv % 16 || out % (Dh == 128 ? 4 : 2)) throw std::invalid_argument("cls_attention: misaligned pointers");
+  if ((long long)B * H > INT_MAX) throw std::invalid_argument("cls_attention: grid too large");
   const int waves = B * H;
-  hipLaunchKernelGGL(cls_attention_kernel, dim3((waves + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  const auto kern = Dh == 32 ? cls_attention_hd_kernel<32> : Dh == 128 ? cls_attention_hd_kernel<128> : cls_attention_kernel;
+  hipLaunchKernelGGL(kern, dim3((waves + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const bf16*>(qkv), reinterpret_cast<const int*>(cu), reinterpret_cast<bf16*>(out),
                      B, H, scale * 1.4426950408889634f);
   FTM_CHECK_LAUNCH();

@@ -246,20 +246,164 @@ __global__ __launch_bounds__(NTH) void attention_causal_kernel(const bf16* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Head dims 32 and 128 (tile<DH>, key_step and store_ctx of attention_tiles.h): the same
+// double-buffered pipeline, four waves, heaviest query block first, with the key block KB chosen so
+// that one ring stage stays 512 16-B chunks of K and of V (two of each per thread, as at 64):
+//   DH = 32:  a workgroup owns the head pair (2p, 2p+1) and 32 queries: wave w is head w & 1 and
+//             query group w >> 1.  KB = 64 keys of 128-B pair rows; LDS as at 64 (44.5 KB, three
+//             workgroups per CU).  An odd H: as in attention.hip, the absent head is zeros in LDS
+//             and is not stored.
+//   DH = 128: one head, 64 queries, 256-B rows, and KB = 32: the ring is 2 x (8 + 9 KB) and the
+//             four P/O slots 17 KB (sized by the 16 x 136 O tile), 52 KB in all, three workgroups
+//             per CU; KB = 64 would take 86 KB and leave one workgroup of four waves on a CU.
+// QB and KB differ now, so the diagonal is walked per 16-key FRAGMENT: wave rows start at fragment
+// fd = (qb QB) / 16 + query group, and in key block j (fragments j F .. j F + F - 1, F = KB / 16) the
+// wave multiplies nf = fd + 1 - j F fragments: nf > F is a block wholly below its diagonal, 1 <= nf
+// <= F holds its diagonal tile as the last fragment, nf <= 0 lies above it and is skipped (the wave
+// still stages and meets the barrier).  Blocks past the end of the sequence are not walked: only
+// rows >= S, which are not stored, could see them.
+template <int DH, int KB>
+struct StagedHd {
+  u32x4 k[2], v[2];
+  float mask;
+};
+
+template <int DH, int KB>
+FTM_DEVICE void load_block_hd(StagedHd<DH, KB>& st, const bf16* __restrict__ kbase, const int* __restrict__ ids, int kb,
+                              int S, int ld, int HD, int vch, int pad_id, int tid) {
+  constexpr int NCH = tile<DH>::NCH;
+  static_assert(KB * NCH == 2 * NTH, "two K and two V chunks per thread and stage");
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int q = tid + it * NTH;
+    const int kg = kb * KB + q / NCH, ch = q % NCH;
+    st.k[it] = u32x4{0u, 0u, 0u, 0u};
+    st.v[it] = u32x4{0u, 0u, 0u, 0u};
+    if (kg < S && ch < vch) {
+      const bf16* row = kbase + (size_t)kg * ld + ch * 8;
+      st.k[it] = *reinterpret_cast<const u32x4*>(row);
+      st.v[it] = *reinterpret_cast<const u32x4*>(row + HD);
+    }
+  }
+  st.mask = 0.f;
+  if (tid < KB) {
+    const int kg = kb * KB + tid;
+    st.mask = (kg < S && ids[kg] != pad_id) ? 0.f : -INFINITY;
+  }
+}
+
+template <int DH, int KB>
+FTM_DEVICE void store_block_hd(const StagedHd<DH, KB>& st, bf16* Ks, bf16* Vs, float* km, int tid) {
+  using T = tile<DH>;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int q = tid + it * NTH;
+    const int key = q / T::NCH, ch = q % T::NCH;
+    *reinterpret_cast<u32x4*>(Ks + T::kswz(key, ch)) = st.k[it];
+    *reinterpret_cast<u32x4*>(Vs + key * T::VP + ch * 8) = st.v[it];
+  }
+  if (tid < KB) km[tid] = st.mask;
+}
+
+template <int DH, int KB>
+__global__ __launch_bounds__(NTH) void attention_causal_hd_kernel(const bf16* __restrict__ qkv,
+                                                                  const int* __restrict__ ids,
+                                                                  bf16* __restrict__ out, int BG, int S, int H,
+                                                                  int pad_id, float scale_log2e) {
+  using T = tile<DH>;
+  constexpr int HP = T::HP;
+  constexpr int QBH = 64 / HP;  // queries per workgroup
+  constexpr int F = KB / 16;    // fragments per key block
+  constexpr int PSLOT = T::pslot(KB);
+  static_assert(F == 2 || F == 4, "the fragment dispatch below");
+  __shared__ __attribute__((aligned(16))) bf16 Ks[2][KB * T::RW];
+  __shared__ __attribute__((aligned(16))) bf16 Vs[2][KB * T::VP];
+  __shared__ __attribute__((aligned(16))) bf16 Ps[4 * PSLOT];
+  __shared__ float kmask[2][KB];
+
+  const int qblocks = (S + QBH - 1) / QBH;
+  const int HG = (H + HP - 1) / HP;
+  const int qb = qblocks - 1 - (int)(blockIdx.x / BG);
+  const int bg = blockIdx.x % BG;
+  const int b = bg / HG, h0 = (bg % HG) * HP;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hp = wave % HP, qg = wave / HP;
+  const int HD = H * DH, ld = 3 * HD;
+  const int vch = min(HP, H - h0) * (DH / 8);
+  const size_t tok0 = (size_t)b * S;
+  const bf16* kbase = qkv + tok0 * ld + HD + h0 * DH;
+  const int* idb = ids + tok0;
+
+  StagedHd<DH, KB> st;
+  load_block_hd<DH, KB>(st, kbase, idb, 0, S, ld, HD, vch, pad_id, tid);
+
+  const int qrow = qb * QBH + qg * 16 + (lane & 15);
+  bf16x8 qa[T::NKS];
+#pragma unroll
+  for (int ks = 0; ks < T::NKS; ++ks) {
+    if (qrow < S && h0 + hp < H)
+      qa[ks] = *reinterpret_cast<const bf16x8*>(qkv + (tok0 + qrow) * ld + (h0 + hp) * DH + ks * 32 + (lane >> 4) * 8);
+    else
+      qa[ks] = bf16x8{};
+  }
+  f32x4 o[T::NO];
+#pragma unroll
+  for (int n = 0; n < T::NO; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float mrow[4], lrow[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    mrow[r] = -INFINITY;
+    lrow[r] = 0.f;
+  }
+  store_block_hd<DH, KB>(st, Ks[0], Vs[0], kmask[0], tid);
+
+  bf16* ps = Ps + wave * PSLOT;
+  const int fd = qb * (QBH / 16) + qg;                                 // the wave's diagonal fragment
+  const int nblk = min((qb * QBH + QBH - 1) / KB + 1, (S + KB - 1) / KB);  // key blocks to walk
+  for (int j = 0; j < nblk; ++j) {
+    const int cur = j & 1;
+    const bool more = j + 1 < nblk;  // block-uniform
+    if (more) load_block_hd<DH, KB>(st, kbase, idb, j + 1, S, ld, HD, vch, pad_id, tid);
+    __syncthreads();
+    const int nf = fd + 1 - j * F;  // wave-uniform
+    if (nf > F) {
+      key_step<DH, F, false>(Ks[cur], Vs[cur], kmask[cur], ps, qa, o, mrow, lrow, lane, hp, scale_log2e);
+    } else if (nf == F) {
+      key_step<DH, F, true>(Ks[cur], Vs[cur], kmask[cur], ps, qa, o, mrow, lrow, lane, hp, scale_log2e);
+    } else if (nf == 1) {
+      key_step<DH, 1, true>(Ks[cur], Vs[cur], kmask[cur], ps, qa, o, mrow, lrow, lane, hp, scale_log2e);
+    } else if constexpr (F == 4) {
+      if (nf == 2) key_step<DH, 2, true>(Ks[cur], Vs[cur], kmask[cur], ps, qa, o, mrow, lrow, lane, hp, scale_log2e);
+      if (nf == 3) key_step<DH, 3, true>(Ks[cur], Vs[cur], kmask[cur], ps, qa, o, mrow, lrow, lane, hp, scale_log2e);
+    }
+    if (more) store_block_hd<DH, KB>(st, Ks[cur ^ 1], Vs[cur ^ 1], kmask[cur ^ 1], tid);
+  }
+  store_ctx<DH>(Ps + (wave - hp) * PSLOT, o, lrow, out + tok0 * HD + h0 * DH, HD, qb * QBH + qg * 16, S, vch, lane, hp);
+}
+
 }  // namespace
 
 void attention_causal_fwd_bf16(uintptr_t qkv, uintptr_t ids, uintptr_t out, int B, int S, int H, int Dh, int pad_id,
                                float scale, uintptr_t stream) {
-  if (Dh != D) throw std::invalid_argument("attention_causal_fwd: head dim must be 64");
+  if (Dh != 32 && Dh != 64 && Dh != 128)
+    throw std::invalid_argument("attention_causal_fwd: head dim must be 32, 64 or 128");
   if (B <= 0 || H <= 0) throw std::invalid_argument("attention_causal_fwd: empty problem");
   if (S < 1 || S > MAX_S) throw std::invalid_argument("attention_causal_fwd: need 1 <= S <= 2048");
   if (!qkv || !ids || !out) throw std::invalid_argument("attention_causal_fwd: null pointer");
+  // rows are H * Dh * 2 bytes, a multiple of 16 for every width: aligned bases suffice
   if (qkv % 16 || out % 16 || ids % 4) throw std::invalid_argument("attention_causal_fwd: misaligned pointers");
-  const long long grid = (long long)B * H * ((S + QB - 1) / QB);
-  if ((long long)B * H > INT_MAX || grid > INT_MAX) throw std::invalid_argument("attention_causal_fwd: grid too large");
-  hipLaunchKernelGGL(attention_causal_kernel, dim3((unsigned)grid), dim3(NTH), 0, reinterpret_cast<hipStream_t>(stream),
+  const int qbh = Dh == 32 ? 32 : QB;                      // queries per workgroup
+  const long long BG = (long long)B * (Dh == 32 ? (H + 1) / 2 : H);  // (batch, head group): pairs at 32
+  const long long grid = BG * ((S + qbh - 1) / qbh);
+  if (BG > INT_MAX || grid > INT_MAX) throw std::invalid_argument("attention_causal_fwd: grid too large");
+  const auto kern = Dh == 32    ? attention_causal_hd_kernel<32, 64>
+                    : Dh == 128 ? attention_causal_hd_kernel<128, 32>
+                                : attention_causal_kernel;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NTH), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const bf16*>(qkv), reinterpret_cast<const int*>(ids),
-                     reinterpret_cast<bf16*>(out), B * H, S, H, pad_id, scale * 1.4426950408889634f);
+                     reinterpret_cast<bf16*>(out), (int)BG, S, H, pad_id, scale * 1.4426950408889634f);
   FTM_CHECK_LAUNCH();
 }
 

@@ -18,7 +18,8 @@ The compiler lowers it to ``embed_ln`` 1, per block the fused QKV ``gemm`` + one
 ``copy`` of the last position and one ``retrieve`` step, so a strict plan holds no glue and never
 writes a ``[B, H, S, S]`` or ``[B, N]`` score tensor.  The output table is the input embedding
 table; ``item_bias[0]`` is a large negative constant so the pad id is never recommended.  The
-hidden size is one of 64, 128, 192, 256 (64-wide heads, ``retrieve``'s ``D <= 256``).
+hidden size is one of 64, 128, 192, 256 (``retrieve``'s ``D <= 256``) and equals ``head_dim * heads``
+with 32-, 64- (the default) or 128-wide heads: SASRec / BERT4Rec sizes such as hidden 64 with 2 heads.
 
 Tensor names: ``item_ids`` (int32 [N, S]), ``scores``, ``top_k`` (``top_k:0`` scores, ``top_k:1``
 item ids).
@@ -50,10 +51,13 @@ class NextItemConfig:
     layers: int = 2
     intermediate: int = 512
     eps: float = 1e-12
+    head_dim: int = 64       # 32, 64 or 128: the widths the attention kernels are built for
 
     def __post_init__(self):
-        if self.hidden not in (64, 128, 192, 256) or self.hidden != 64 * self.heads:
-            raise ValueError("NextItemConfig: hidden must be 64 * heads, one of 64, 128, 192, 256")
+        if self.head_dim not in (32, 64, 128):
+            raise ValueError("NextItemConfig: head_dim must be 32, 64 or 128")
+        if self.hidden not in (64, 128, 192, 256) or self.hidden != self.head_dim * self.heads:
+            raise ValueError(f"NextItemConfig: hidden must be {self.head_dim} * heads, one of 64, 128, 192, 256")
 
 
 def init_next_item_weights(cfg: NextItemConfig, seq_len: int, seed: int = 0) -> dict[str, torch.Tensor]:

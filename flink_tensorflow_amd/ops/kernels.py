@@ -2247,6 +2247,7 @@ def softmax_topk(logits: torch.Tensor, k: int, want_probs: bool = False, vals=No
 
 # ------------------------------------------------------------------------------ attention
 CAUSAL_ATTENTION_MAX_SEQ = 2048  # longest sequence of the causal attention kernel
+ATTENTION_HEAD_DIMS = (32, 64, 128)  # head widths the attention kernels are built for
 
 
 def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int, heads: int, pad_id: int = 0,
@@ -2254,13 +2255,14 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
               cu_seqlens: torch.Tensor | None = None, causal: bool = False) -> torch.Tensor:
     """Multi-head self-attention over the fused QKV projection output.
 
-    Padded batch: ``qkv`` [B*S, 3*H*64] bf16 (Q|K|V blocks, head h at h*64), ``ids`` [B*S]
+    Padded batch: ``qkv`` [B*S, 3*H*Dh] bf16 (Q|K|V blocks, head h at h*Dh; on the GPU ``Dh`` is
+    one of ``ATTENTION_HEAD_DIMS``, anything else is a ``ValueError``), ``ids`` [B*S]
     int32 token ids (keys whose id == ``pad_id`` are masked).  Packed batch
     (``cu_seqlens`` [B+1] int32 given, ``seq`` = the longest sequence): sequence b is rows
     ``cu[b]:cu[b+1]`` of ``qkv``, no padding; rows past ``cu[B]`` are left untouched.
     ``causal`` (padded batch only, ``1 <= S <= 2048``): query i attends key j iff ``j <= i`` and key
     j is not padding, on ``kernels/attention_causal.hip``; a query with no admissible key gets a
-    zero row.  Returns ctx [rows, H*64]."""
+    zero row.  Returns ctx [rows, H*Dh]."""
     if causal and cu_seqlens is not None:
         raise ValueError("attention: causal attention of a packed batch (cu_seqlens) is not supported")
     if causal and not 1 <= seq <= CAUSAL_ATTENTION_MAX_SEQ:  # the kernel's envelope, on the host path too
@@ -2277,6 +2279,8 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
     if out is None:
         out = torch.empty((T, heads * Dh), dtype=qkv.dtype, device=qkv.device)
     if qkv.is_cuda:
+        if Dh not in ATTENTION_HEAD_DIMS:
+            raise ValueError(f"attention: head dim {Dh} is not one of {ATTENTION_HEAD_DIMS}")
         _check(qkv, "qkv", device=qkv.device)
         _check(out, "out", device=qkv.device)
         if cu_seqlens is not None:
@@ -2317,7 +2321,8 @@ CLS_ATTENTION_MAX_SEQ = 512  # keys per sequence the cls_attention kernel holds 
 def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: int, heads: int,
                   scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Attention of each packed sequence's FIRST token only (the classifier's final layer):
-    ``qkv`` [T, 3*H*64] packed rows, ``cu_seqlens`` [B+1] → [B, H*64].  ``seq`` is the
+    ``qkv`` [T, 3*H*Dh] packed rows, ``cu_seqlens`` [B+1] → [B, H*Dh] (on the GPU ``Dh`` is one of
+    ``ATTENTION_HEAD_DIMS``, anything else is a ``ValueError``).  ``seq`` is the
     longest possible sequence, as for ``attention``; the kernel keeps a sequence's scores in
     LDS and handles at most 512 keys, so ``seq`` > 512 raises ``ValueError`` on the device
     and on the host path alike (no sequence is ever silently truncated)."""
@@ -2329,6 +2334,8 @@ def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: 
     if out is None:
         out = torch.empty((batch, heads * Dh), dtype=qkv.dtype, device=qkv.device)
     if qkv.is_cuda:
+        if Dh not in ATTENTION_HEAD_DIMS:
+            raise ValueError(f"cls_attention: head dim {Dh} is not one of {ATTENTION_HEAD_DIMS}")
         _check(qkv, "qkv", device=qkv.device)
         _check(out, "out", device=qkv.device)
         _check(cu_seqlens, "cu_seqlens", torch.int32, qkv.device)
