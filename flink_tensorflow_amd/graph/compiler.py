@@ -142,7 +142,7 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
-                 arena=None, token_capacity: int | None = None):
+                 arena=None, token_capacity: int | None = None, pack_causal: bool = False):
         if precision not in ("bf16", "fp8"):
             raise ValueError(f"precision must be bf16 or fp8, not {precision!r}")
         from .control_flow import fold_static_control_flow
@@ -158,6 +158,7 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
         self.arena = arena  # subtask DeviceArena (shared slab + interned weights) or None
         # padding-free transformer plan: token rows packed into this capacity (graph/packed.py)
         self.token_cap = token_capacity
+        self.pack_causal = pack_causal  # opt-in: causal attention groups may run token-packed too
         self._pack: dict | None = None
         self._cls_nodes: set[str] = set()
         self._cur_cls = False
@@ -326,7 +327,7 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
     def _get(self, src: tuple[str, int]) -> Val | None:
         v = self.vals.get(src)
         if v is not None and self._cur_cls and v.rows == "packed":
-            return self._cls_gather(v)  # first-token-only region: read each sequence's first row
+            return self._cls_gather(v)  # one-token-only region: read each sequence's first (or last) row
         return v if v is not None else self._const_val(src)
 
     def _single_consumer(self, name: str) -> Node | None:

@@ -8,7 +8,9 @@ staging slot the runner already holds, so no device synchronisation — and pick
 smallest capacity that holds them; the plan's own ``pack_tokens`` kernel then compacts the
 same tokens on the device.  Every projection, LayerNorm and attention runs on the packed
 rows only, and the final layer after its QKV projection on one row per sequence
-(``graph/transformer_lowering.py``).
+(``graph/transformer_lowering.py``).  ``pack_causal=True`` admits causal transformers (next-item
+models): packed causal attention, and the last block after its QKV projection on each sequence's
+last row.
 
 It implements the plan protocol of ``batching.engine.PipelinedGpuRunner``
 (``input_buffer`` / ``replay`` / ``output_tensors`` / ``select``) and ``__call__`` like a
@@ -28,7 +30,7 @@ from .compiler import CompiledFunction, CompileError
 class PackedFunction:
     def __init__(self, graph, feeds: dict, fetches: list[str], device, variables: dict | None = None,
                  use_graph: bool = True, strict: bool = False, arena=None, granule: int = 2048,
-                 capacities=None):
+                 capacities=None, pack_causal: bool = False):
         if len(feeds) != 1:
             raise CompileError("token packing takes exactly one feed (the token ids)")
         (feed, (shape, _)), = feeds.items()
@@ -44,7 +46,8 @@ class PackedFunction:
         self.plans: dict[int, CompiledFunction] = {}
         for c in reversed(self.caps):  # largest first: every capacity shares the first slab
             self.plans[c] = CompiledFunction(graph, feeds, fetches, device, variables, use_graph=use_graph,
-                                             strict=strict, arena=arena, token_capacity=c)
+                                             strict=strict, arena=arena, token_capacity=c,
+                                             pack_causal=pack_causal)
         self.plans = dict(sorted(self.plans.items()))
         self.pad = self.plans[full]._pack["pad"]
         self.current = self.plans[full]

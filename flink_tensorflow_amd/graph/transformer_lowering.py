@@ -22,7 +22,8 @@ Google's ``modeling.py``) arrives as decomposed ops.  Before lowering, the compi
   ``causal_attention`` launch (``kernels/attention_causal.hip``, ``S <= 2048``).  Any other
   constant (upper or strict lower triangle, a band, a shifted diagonal, values other than 0/1)
   matches nothing and the ``BatchMatMul`` / ``Softmax`` chain stays glue, as do a causal mask
-  with no key mask and one given as a second adder.  Causal graphs do not token-pack;
+  with no key mask and one given as a second adder.  Causal graphs token-pack on request only
+  (``pack_causal``, below);
 * embeddings without a token-type row (``GatherV2 + positions -> layer_norm``, an item or event
   embedding) take the same ``embed_layernorm`` launch with a zero type row;
 * GELU — BERT's tanh form after a ``MatMul+BiasAdd`` -> the GEMM's GELU epilogue;
@@ -46,6 +47,18 @@ per sequence — ``cls_attention`` (first query over the sequence's keys), then 
 projection, residual LayerNorm, FFN and LayerNorm on B rows, with each packed operand read
 through a first-row gather.  The reference product path this accelerates is
 ``ModelFunction`` over a loaded signature (``ModelFunction.scala:34-79``).
+
+**Causal packing** (``pack_causal=True``, opt-in; without it a causal group or a last-token slice
+is a ``CompileError`` under packing, as before): causal groups are accepted under the encoder
+conditions and lower to the QKV ``gemm`` on packed rows + ``packed_causal_attention``
+(``kernels/attention_causal_packed.hip``); a ``packed_rows`` step behind ``pack_tokens`` writes the
+per-row sequence starts that kernel masks by and each sequence's last row.  A ``StridedSlice`` of the
+LAST position (begin ``S - 1`` or ``-1``) is a gather by those last rows and marks a last-token-only
+region through the same walk: the final block's attention becomes ``last_attention`` (one query per
+sequence; ``S <= 512``, above that no region forms and the slice gathers behind the full step) and
+everything after it runs on B rows.  First- and last-token slices in one graph, and a slice of any
+other position, stay a ``CompileError``; a first-token region never reaches through a causal group
+(its first row sees itself only).
 """
 from __future__ import annotations
 
@@ -318,8 +331,9 @@ class TransformerLowering:
         attns = [g for g in grps if g["kind"] == "attn"]
         if len(embs) != 1 or not attns:
             raise CompileError("token packing needs one embedding group and fused attention")
-        if any(g.get("causal") for g in attns):
-            raise CompileError("token packing does not cover causal attention (no packed causal kernel)")
+        causal = any(g.get("causal") for g in attns)
+        if causal and not self.pack_causal:
+            raise CompileError("token packing of causal attention is opt-in (pack_causal=True)")
         ids_src = embs[0]["ids"]
         feed = f"{ids_src[0]}:{ids_src[1]}"  # feed names are normalised to ``node:index``
         if feed not in self.feed_names:
@@ -334,13 +348,29 @@ class TransformerLowering:
         T = int(self.token_cap)
         if not 0 < T <= B * S:
             raise CompileError(f"token capacity {T} outside (0, {B * S}]")
-        self._pack = {"ids": ids_src, "feed": feed, "B": B, "S": S, "T": T, "pad": 0, "cu": None, "cls": None}
-        # first-token-only region: nodes whose every consumer is in the region or is the
-        # pooler's first-token slice (reverse topological order: consumers first)
-        starts = {n for n in self.order if self.graph[n].op == "StridedSlice" and self._first_token_spec(self.graph[n])}
+        # "token": which row of a sequence the one-token slices read ("first" / "last" / None); "one":
+        # that row's index per sequence (pack_tokens' ``cls`` or packed_rows' ``last``); "seq_start":
+        # packed_rows' per-row sequence starts, present when a causal group or a last-token slice needs them
+        self._pack = {"ids": ids_src, "feed": feed, "B": B, "S": S, "T": T, "pad": 0, "cu": None, "one": None,
+                      "token": None, "seq_start": None, "rows": causal}
+        # one-token-only region: nodes whose every consumer is in the region or is the one-token
+        # slice (the pooler's first token, or a next-item head's last event; reverse topological
+        # order: consumers first)
+        specs = {n: self._one_token_spec(self.graph[n], S) for n in self.order if self.graph[n].op == "StridedSlice"}
+        starts = {n for n, t in specs.items() if t}
         if not starts:
             return
-        attn_out = {g["out"]: g for g in attns}
+        if len({specs[n] for n in starts}) > 1:
+            raise CompileError("token packing serves first-token or last-token slices, not both in one graph")
+        token = self._pack["token"] = specs[next(iter(starts))]
+        if token == "last":
+            if not self.pack_causal:
+                raise CompileError("a last-token slice of packed rows is opt-in (pack_causal=True)")
+            self._pack["rows"] = True
+            if S > K.CLS_ATTENTION_MAX_SEQ:  # no one-query kernel: the slice is a gather behind the full step
+                return
+        # the first row of a causal sequence sees itself only: no first-token region through causal attention
+        attn_out = {g["out"]: g for g in attns if token == "last" or not g.get("causal")}
         fed = {TensorName.parse(f).name for f in self.feed_names}
         region: set[str] = set()
         barrier: set[str] = set()
@@ -369,41 +399,46 @@ class TransformerLowering:
             region.add(n)
         self._cls_nodes = region
 
-    def _first_token_spec(self, node) -> bool:
-        """``x[:, 0:1, :]`` / ``x[:, 0, :]`` of a rank-3 tensor (constant bounds, unit strides)."""
+    def _one_token_spec(self, node, S: int) -> str | None:
+        """"first" for ``x[:, 0:1, :]`` / ``x[:, 0, :]``, "last" for ``x[:, S-1:S, :]`` / ``x[:, S-1, :]``
+        (begin ``S - 1`` or ``-1``) of a rank-3 tensor with ``S`` positions (constant bounds, unit
+        strides); None for anything else."""
         if len(node.inputs) != 4 or node.attr("ellipsis_mask", 0) or node.attr("new_axis_mask", 0):
-            return False
+            return None
         if self._is_const_node(node.inputs[0]):
-            return False
+            return None
         b, e, s = (self._const_of(node.inputs[i]) for i in (1, 2, 3))
         if b is None or e is None or s is None:
-            return False
+            return None
         b, e, s = (t.reshape(-1).tolist() for t in (b, e, s))
         if len(b) != 3 or any(v != 1 for v in s):
-            return False
+            return None
         bm, em, shrink = node.attr("begin_mask", 0), node.attr("end_mask", 0), node.attr("shrink_axis_mask", 0)
-        full = all((bm >> d & 1 or b[d] == 0) and em >> d & 1 and not shrink >> d & 1 for d in (0, 2))
-        first = not bm >> 1 & 1 and b[1] == 0 and (shrink >> 1 & 1 or (not em >> 1 & 1 and e[1] == 1))
-        return full and first
+        if not all((bm >> d & 1 or b[d] == 0) and em >> d & 1 and not shrink >> d & 1 for d in (0, 2)) or bm >> 1 & 1:
+            return None
+        one, open_end = shrink >> 1 & 1, em >> 1 & 1
+        if b[1] == 0 and (one or (not open_end and e[1] == 1)):
+            return "first"
+        if b[1] in (S - 1, -1) and (one or open_end or e[1] == S):
+            return "last"
+        return None
 
     def _cls_gather(self, v):
-        """(B, D) rows of each sequence's first token of the packed ``v`` (one gather step,
-        cached per value)."""
+        """(B, D) rows of each sequence's first (or last: ``pack["token"]``) token of the packed
+        ``v`` (one gather step, cached per value)."""
         hit = self._cls_cache.get(id(v))
         if hit is not None:
             return hit
         pk = self._pack
         out = self._new((pk["B"], v.shape[-1]), v.dtype)
         out.rows, out.lshape = "cls", v.lshape
-        cls = pk["cls"]
-
-        from ..ops import kernels as K
+        cls = pk["one"]
 
         def run(v=v, out=out, cls=cls):
             src = _view(v)
             K.gather_rows(src.reshape(-1, src.shape[-1]), cls.buf, out=out.buf)
 
-        self._emit(f"first_token_gather/{len(self._cls_cache)}", "gather", run, [v, cls], [out])
+        self._emit(f"{pk['token']}_token_gather/{len(self._cls_cache)}", "gather", run, [v, cls], [out])
         self._cls_cache[id(v)] = out
         return out
 
@@ -423,8 +458,10 @@ class TransformerLowering:
         self.vals[(node.name, 0)] = Val(tuple(x.shape), x.dtype, alias_of=x, rows=x.rows, lshape=tuple(shape))
 
     def _slice_first_token(self, node, x) -> bool:
-        if not self._first_token_spec(node) or x.lshape is None or len(x.lshape) != 3:
-            raise CompileError(f"StridedSlice {node.name} of packed token rows is not a first-token slice")
+        pk = self._pack
+        if pk["token"] is None or self._one_token_spec(node, pk["S"]) != pk["token"] or x.lshape is None \
+                or len(x.lshape) != 3:
+            raise CompileError(f"StridedSlice {node.name} of packed token rows is not a first- or last-token slice")
         if x.rows == "packed":
             x = self._cls_gather(x)
         B, D = self._pack["B"], x.shape[-1]
@@ -514,12 +551,22 @@ class TransformerLowering:
             T = pk["T"]
             pids, ppos = self._new((T,), torch.int32), self._new((T,), torch.int32)
             cu, cls = self._new((B + 1,), torch.int32), self._new((B,), torch.int32)
-            pk["cu"], pk["cls"] = cu, cls
+            pk["cu"], pk["one"] = cu, cls
 
             def run_pack(ids=ids32, pids=pids, ppos=ppos, cu=cu, cls=cls):
                 K.pack_tokens(_view(ids).reshape(B, S), pk["pad"], T, pids.buf, ppos.buf, cu.buf, cls.buf)
 
             self._emit(grp["out"] + "/pack_tokens", "pack", run_pack, [ids32], [pids, ppos, cu, cls])
+            if pk["rows"]:  # causal groups / a last-token slice: per-row sequence starts, last rows
+                start, last = self._new((T,), torch.int32), self._new((B,), torch.int32)
+                pk["seq_start"] = start
+                if pk["token"] == "last":
+                    pk["one"] = last
+
+                def run_rows(cu=cu, start=start, last=last):
+                    K.packed_rows(cu.buf, B, T, start.buf, last.buf)
+
+                self._emit(grp["out"] + "/packed_rows", "packed_rows", run_rows, [cu], [start, last])
             out = self._new((T, D))
             out.rows, out.lshape = "packed", (B, S, D)
 
@@ -580,7 +627,7 @@ class TransformerLowering:
                 any(w.shape != (H, Din) for w in ws):
             return False
         causal = grp.get("causal", False)
-        if causal and (pk is not None or S > K.CAUSAL_ATTENTION_MAX_SEQ
+        if causal and ((pk is not None and pk["seq_start"] is None) or S > K.CAUSAL_ATTENTION_MAX_SEQ
                        or not _is_tril(self._const_of(grp["tril"]), S)):  # the folded constant, checked again
             return False
         w_qkv = self._dev(torch.cat(ws, 0), torch.bfloat16)
@@ -604,12 +651,15 @@ class TransformerLowering:
             else:
                 K.gemm(_rows(xin, Din), w_qkv, b_qkv, out=qkv.buf)
 
+        one = K.last_attention if pk is not None and pk["token"] == "last" else K.cls_attention
         if pk is not None:
-            cu = pk["cu"]
+            cu, start = pk["cu"], pk["seq_start"]
 
             def run_attn(qkv=qkv, ctx=ctx, cu=cu):
-                if cls_only:  # first query of each sequence only (the pooler reads nothing else)
-                    K.cls_attention(qkv.buf, cu.buf, B, S, nh, scale=sc, out=ctx.buf)
+                if cls_only:  # one query per sequence (the fetches read nothing else): its first or last row
+                    one(qkv.buf, cu.buf, B, S, nh, scale=sc, out=ctx.buf)
+                elif causal:
+                    K.packed_causal_attention(qkv.buf, cu.buf, start.buf, B, nh, scale=sc, out=ctx.buf)
                 else:
                     K.attention(qkv.buf, None, B, S, nh, scale=sc, out=ctx.buf, cu_seqlens=cu.buf)
 
@@ -619,9 +669,15 @@ class TransformerLowering:
                 K.attention(qkv.buf, _view(mask).reshape(-1), B, S, nh, pad_id=0, scale=sc, out=ctx.buf,
                             causal=causal)
 
-        kind = "cls_attention" if cls_only else "causal_attention" if causal else "attention"
+        if cls_only:
+            kind = "last_attention" if one is K.last_attention else "cls_attention"
+        elif causal:
+            kind = "packed_causal_attention" if pk is not None else "causal_attention"
+        else:
+            kind = "attention"
+        ins = [qkv, mask] + ([pk["seq_start"]] if kind == "packed_causal_attention" else [])
         self._emit(grp["out"] + "/qkv", "gemm", run_qkv, [xin], [qkv], {"impl": "gemm_pp", "fused": "qkv"})
-        self._emit(grp["out"], kind, run_attn, [qkv, mask], [ctx])
+        self._emit(grp["out"], kind, run_attn, ins, [ctx])
         self.vals[(grp["out"], 0)] = ctx
         return True
 

@@ -408,6 +408,12 @@ __global__ __launch_bounds__(1024) void pack_tokens_kernel(const int* __restrict
 // over coalesced 128-B V rows.  out [B, H*64] bf16.  The scores of a sequence live in a
 // 512-float LDS row per wave: sequences are at most 512 keys long (ops.kernels.cls_attention
 // refuses a longer ``seq``); the min() below only keeps a bad cu_seqlens inside that row.
+//
+// LAST picks the query row at compile time: false is the sequence's first row (cls_attention),
+// true its last one, row cu[b+1] - 1 (last_attention: the final block of a causal transformer
+// whose fetches read the last event only; that row may attend every key of its sequence, so the
+// causal mask is vacuous and the kernel is the same).
+template <bool LAST>
 __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restrict__ qkv, const int* __restrict__ cu,
                                                             bf16* __restrict__ out, int B, int H, float scale_log2e) {
   __shared__ float probs[4][512];
@@ -422,7 +428,7 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restri
     out[(size_t)b * H * D + h * D + lane] = f2bf(0.f);
     return;
   }
-  const bf16* qrow = qkv + (size_t)t0 * ld + h * D;
+  const bf16* qrow = qkv + (size_t)(LAST ? t0 + n - 1 : t0) * ld + h * D;
   float q[D];
 #pragma unroll
   for (int c = 0; c < D / 8; ++c) {
@@ -468,7 +474,7 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restri
 //             and softmax would double); instead the idle half takes every second key: lane l
 //             owns column l & 31 over the keys of parity l >> 5, and one __shfl_xor(32) adds the
 //             two partial sums, so all 64 lanes load on every step.
-template <int DH>
+template <int DH, bool LAST>
 __global__ __launch_bounds__(256) void cls_attention_hd_kernel(const bf16* __restrict__ qkv,
                                                                const int* __restrict__ cu, bf16* __restrict__ out,
                                                                int B, int H, float scale_log2e) {
@@ -483,14 +489,15 @@ __global__ __launch_bounds__(256) void cls_attention_hd_kernel(const bf16* __res
   const int t0 = cu[b];
   const int n = min(cu[b + 1] - t0, 512);
   bf16* orow = out + (size_t)b * HD + h * DH;
-  const bf16* qrow = qkv + (size_t)t0 * ld + h * DH;
+  const bf16* base = qkv + (size_t)t0 * ld + h * DH;  // Q of the sequence's first row; K, V lie HD, 2 HD further
   float mx = -INFINITY, sum = 0.f;
   if (n > 0) {  // an empty sequence reads nothing (row t0 may lie one past the batch)
     bf16x8 qv[DH / 8];
 #pragma unroll
-    for (int c = 0; c < DH / 8; ++c) qv[c] = *reinterpret_cast<const bf16x8*>(qrow + c * 8);
+    for (int c = 0; c < DH / 8; ++c)
+      qv[c] = *reinterpret_cast<const bf16x8*>(base + (LAST ? (size_t)(n - 1) * ld : 0) + c * 8);
     for (int j = lane; j < n; j += 64) {
-      const bf16* krow = qrow + (size_t)j * ld + HD;
+      const bf16* krow = base + (size_t)j * ld + HD;
       float sdot = 0.f;
 #pragma unroll
       for (int c = 0; c < DH / 8; ++c) {
@@ -513,7 +520,7 @@ __global__ __launch_bounds__(256) void cls_attention_hd_kernel(const bf16* __res
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's probabilities are in LDS
   const float inv = n > 0 ? 1.f / sum : 0.f;
-  const bf16* vbase = qrow + 2 * HD;
+  const bf16* vbase = base + 2 * HD;
   if constexpr (DH == 128) {
     float a0 = 0.f, a1 = 0.f;
     for (int j = 0; j < n; ++j) {
@@ -610,23 +617,41 @@ void embed_ln_bf16(uintptr_t ids, uintptr_t tt, uintptr_t pos_ids, uintptr_t wor
   FTM_CHECK_LAUNCH();
 }
 
-void cls_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale,
-                        uintptr_t stream) {
+namespace {
+
+template <bool LAST>
+void launch_one_query(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale, uintptr_t stream) {
   if (Dh != 32 && Dh != 64 && Dh != 128) throw std::invalid_argument("cls_attention: head dim must be 32, 64 or 128");
   if (B <= 0 || H <= 0 || !cu) throw std::invalid_argument("cls_attention: empty problem / no cu_seqlens");
   // 16-B loads of q and k; the output row is stored 2 B per lane (4 B at 128: two columns a lane)
   if (qkv % 16 || out % (Dh == 128 ? 4 : 2)) throw std::invalid_argument("cls_attention: misaligned pointers");
   if ((long long)B * H > INT_MAX) throw std::invalid_argument("cls_attention: grid too large");
   const int waves = B * H;
-  const auto kern = Dh == 32 ? cls_attention_hd_kernel<32> : Dh == 128 ? cls_attention_hd_kernel<128> : cls_attention_kernel;
+  const auto kern = Dh == 32    ? cls_attention_hd_kernel<32, LAST>
+                    : Dh == 128 ? cls_attention_hd_kernel<128, LAST>
+                                : cls_attention_kernel<LAST>;
   hipLaunchKernelGGL(kern, dim3((waves + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const bf16*>(qkv), reinterpret_cast<const int*>(cu), reinterpret_cast<bf16*>(out),
                      B, H, scale * 1.4426950408889634f);
   FTM_CHECK_LAUNCH();
 }
 
+}  // namespace
+
+void cls_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale,
+                        uintptr_t stream) {
+  launch_one_query<false>(qkv, cu, out, B, H, Dh, scale, stream);
+}
+
+// the same kernels with each sequence's LAST row as the query
+void last_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale,
+                         uintptr_t stream) {
+  launch_one_query<true>(qkv, cu, out, B, H, Dh, scale, stream);
+}
+
 void register_attention(pybind11::module_& m) {
   m.def("cls_attention_bf16", &cls_attention_bf16);
+  m.def("last_attention_bf16", &last_attention_bf16);
   m.def("attention_fwd_bf16", &attention_fwd_bf16);
   m.def("embed_ln_bf16", &embed_ln_bf16);
   m.def("pack_tokens", &pack_tokens);

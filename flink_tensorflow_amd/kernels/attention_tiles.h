@@ -1,4 +1,5 @@
-// LDS tile helpers shared by the attention kernels (attention.hip, attention_causal.hip): K rows
+// LDS tile helpers shared by the attention kernels (attention.hip, attention_causal.hip,
+// attention_causal_packed.hip): K rows
 // chunk-swizzled for conflict-free b128 fragment reads, V and P^T read through the hardware
 // transpose read as MFMA operands.  The 64-wide kernels use the constants right below; the 32- and
 // 128-wide kernels use tile<DH> and the key_step / store_ctx pieces at the end of this header.
@@ -62,7 +63,9 @@ FTM_DEVICE bf16x8 tr_read8(const bf16* p, int pitch) {
 // the group and query group w / HP (16 rows).
 template <int DH>
 struct tile {
-  static_assert(DH == 32 || DH == 128, "the 64-wide kernels use D, VP, OP and kswz above");
+  // tile<64> is the 64-wide constants above (D, VP, OP, kswz) under the names of this struct, for
+  // kernels templated over the head dim (attention_causal_packed.hip)
+  static_assert(DH == 32 || DH == 64 || DH == 128, "head dims the attention kernels are built for");
   static constexpr int HP = DH == 32 ? 2 : 1;        // heads per workgroup = heads per LDS row
   static constexpr int RW = DH * HP;                 // LDS row width (elements): 64 or 128
   static constexpr int NCH = RW / 8;                 // 16-B chunks per row: 8 or 16
@@ -71,7 +74,7 @@ struct tile {
   static constexpr int NKS = DH / 32;                // MFMA K-steps of S = Q K^T per key fragment
   static constexpr int NO = DH / 16;                 // output fragments per wave
   static FTM_DEVICE int kswz(int row, int chunk) {
-    return row * RW + ((chunk ^ (DH == 32 ? (row >> 1) & 7 : row & 15)) << 3);
+    return row * RW + ((chunk ^ (DH == 32 ? (row >> 1) & 7 : DH == 64 ? row & 7 : row & 15)) << 3);
   }
   // per-wave P^T slot for KB keys; it must also hold the wave's share of the O staging tile
   // ([16][OP], shared by the HP waves of a query group)
@@ -82,10 +85,16 @@ struct tile {
 // is staged, so the PV step of an odd NF reads a zeroed P fragment against real V rows).  With
 // DIAG the last fragment, n == NF - 1, is the wave's own 16 x 16 diagonal tile and takes the
 // key > query compare; the fragments before it lie wholly below the diagonal.
-template <int DH, int NF, bool DIAG>
+//
+// PACKED (token-packed causal attention): there is no key mask (``km`` is not read); with LOWER a
+// key is also masked when it lies before the start of the row's sequence, ``key0 + key <
+// start[r]`` with ``key0`` the block's first row of the token stream and ``start`` the sequence
+// starts of the lane's four accumulator rows.  Both flags off is the code of the padded kernels.
+template <int DH, int NF, bool DIAG, bool PACKED = false, bool LOWER = false>
 FTM_DEVICE void key_step(const bf16* Ks, const bf16* Vs, const float* km, bf16* ps,
                          const bf16x8 (&qa)[tile<DH>::NKS], f32x4 (&o)[tile<DH>::NO], float (&mrow)[4],
-                         float (&lrow)[4], int lane, int hp, float scale_log2e) {
+                         float (&lrow)[4], int lane, int hp, float scale_log2e, int key0 = 0,
+                         const int* start = nullptr) {
   using T = tile<DH>;
   constexpr int NPV = (NF + 1) / 2;  // PV steps of 32 keys
   const int col = lane & 15, rbase = (lane >> 4) * 4;
@@ -107,8 +116,11 @@ FTM_DEVICE void key_step(const bf16* Ks, const bf16* Vs, const float* km, bf16* 
     float mx = -INFINITY;
 #pragma unroll
     for (int n = 0; n < NF; ++n) {
-      float v = s[n][r] * scale_log2e + km[n * 16 + col];
+      float v;
+      if constexpr (PACKED) v = s[n][r] * scale_log2e;
+      else v = s[n][r] * scale_log2e + km[n * 16 + col];
       if (DIAG && n == NF - 1 && col > rbase + r) v = -INFINITY;  // key > query, same 16 x 16 tile
+      if (LOWER && key0 + n * 16 + col < start[r]) v = -INFINITY;  // key of an earlier sequence
       s[n][r] = v;
       mx = fmaxf(mx, v);
     }

@@ -16,6 +16,7 @@ void register_embedding(pybind11::module_& m);
 void register_fp8(pybind11::module_& m);
 void register_attention(pybind11::module_& m);
 void register_attention_causal(pybind11::module_& m);
+void register_attention_causal_packed(pybind11::module_& m);
 void register_dconv(pybind11::module_& m);
 void register_elementwise(pybind11::module_& m);
 void register_conv3x3c64(pybind11::module_& m);
@@ -50,6 +51,7 @@ PYBIND11_MODULE(_hip, m) {
   register_fp8(m);
   register_attention(m);
   register_attention_causal(m);
+  register_attention_causal_packed(m);
   register_dconv(m);
   register_elementwise(m);
   register_conv3x3c64(m);

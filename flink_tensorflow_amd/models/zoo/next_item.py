@@ -21,6 +21,11 @@ table; ``item_bias[0]`` is a large negative constant so the pad id is never reco
 hidden size is one of 64, 128, 192, 256 (``retrieve``'s ``D <= 256``) and equals ``head_dim * heads``
 with 32-, 64- (the default) or 128-wide heads: SASRec / BERT4Rec sizes such as hidden 64 with 2 heads.
 
+``NextItemModel(pack_tokens=True)`` serves the same graph padding-free (``graph/packed.py`` with
+``pack_causal=True``): ``pack_tokens`` + ``packed_rows`` + ``embed_ln`` at each event's own position,
+every block on the real events only (``packed_causal_attention``), and the last block after its QKV
+projection on one row per session (``last_attention``, then projections and LayerNorms on B rows).
+
 Tensor names: ``item_ids`` (int32 [N, S]), ``scores``, ``top_k`` (``top_k:0`` scores, ``top_k:1``
 item ids).
 """
@@ -85,10 +90,12 @@ def init_next_item_weights(cfg: NextItemConfig, seq_len: int, seed: int = 0) -> 
 
 
 def next_item_graph_def(cfg: NextItemConfig | None = None, seq_len: int = 64, k: int = 10, seed: int = 0,
-                        weights: dict | None = None, causal_const: np.ndarray | None = None) -> GraphDef:
+                        weights: dict | None = None, causal_const: np.ndarray | None = None,
+                        query_pos: int | None = None) -> GraphDef:
     """The frozen graph on ``[B, seq_len]`` ids (B dynamic) with ``k`` recommendations per record.
     ``weights`` replaces ``init_next_item_weights(cfg, seq_len, seed)``; ``causal_const`` replaces
-    the ``[1, 1, S, S]`` lower-triangular ones constant of the attention mask."""
+    the ``[1, 1, S, S]`` lower-triangular ones constant of the attention mask, ``query_pos`` the
+    position ``S - 1`` whose hidden state is the query."""
     cfg = cfg or NextItemConfig()
     w = weights if weights is not None else init_next_item_weights(cfg, seq_len, seed)
     S, H = seq_len, cfg.hidden
@@ -121,8 +128,9 @@ def next_item_graph_def(cfg: NextItemConfig | None = None, seq_len: int = 64, k:
     x2 = b.reshape(x, [-1, H], name="next_item/encoder/Reshape")
     x2 = encoder_layers(b, W, x2, adder, S, H, cfg.heads, cfg.layers, cfg.eps, scope="next_item/encoder/")
     seq = b.reshape(x2, [-1, S, H], name="next_item/encoder/Reshape_out")
-    last = b.op("StridedSlice", [seq, _c(b, "next_item/last/stack", np.asarray([0, S - 1, 0], np.int32)),
-                                 _c(b, "next_item/last/stack_1", np.asarray([0, S, 0], np.int32)),
+    qp = S - 1 if query_pos is None else query_pos
+    last = b.op("StridedSlice", [seq, _c(b, "next_item/last/stack", np.asarray([0, qp, 0], np.int32)),
+                                 _c(b, "next_item/last/stack_1", np.asarray([0, qp + 1, 0], np.int32)),
                                  _c(b, "next_item/last/stack_2", np.asarray([1, 1, 1], np.int32))],
                 name="next_item/last", T=DataType.FLOAT, Index=DataType.INT32, begin_mask=5, end_mask=5,
                 ellipsis_mask=0, new_axis_mask=0, shrink_axis_mask=2)
@@ -137,13 +145,21 @@ class NextItemModel(GenericModel, BatchedGpuModel):
     ``(score, item_id)`` pairs, best first.  The host keeps the most recent ``seq_len`` events and
     left-pads with 0.  On a GPU subtask ``open()`` compiles one strict plan per batch bucket and
     compute lane and serves them through the pipelined runner; on a host subtask the graph runs in
-    the interpreter."""
+    the interpreter.  ``pack_tokens=True``: each bucket is a padding-free ``PackedFunction`` with
+    ``PACK_CAPACITIES`` token capacities (the host counts a batch's events and picks the smallest
+    that holds them)."""
+
+    # token capacities per bucket of a packed model: evenly spaced multiples of 64 (the packed causal
+    # kernel's row tile).  ``default_granule`` is BERT-sized (2048-token steps: one capacity at 32 x 64).
+    # Four keeps compile time and captured graphs at 4 x the padded model's per bucket and bounds
+    # the padding at a quarter of the bucket; the count is a choice, not a measured optimum.
+    PACK_CAPACITIES = 4
 
     _TRANSIENT = ("_graph", "_session", "_plans", "_runner", "_arena")
 
     def __init__(self, cfg: NextItemConfig | None = None, seq_len: int = 64, top_k: int = 10,
                  buckets: Sequence[int] = (32, 256), seed: int = 0, weights: dict | None = None, device=None,
-                 depth: int = 3, use_graph: bool = True, lanes: int = 2):
+                 depth: int = 3, use_graph: bool = True, lanes: int = 2, pack_tokens: bool = False):
         super().__init__(device)
         self.cfg = cfg or NextItemConfig()
         self.seq_len, self.top_k = seq_len, top_k
@@ -152,6 +168,7 @@ class NextItemModel(GenericModel, BatchedGpuModel):
         self.depth = depth
         self.use_graph = use_graph
         self.lanes = max(1, int(lanes))
+        self.pack_tokens = pack_tokens
         self.feed = "item_ids:0"
         self.fetches = ["top_k:0", "top_k:1"]
         self._plans: dict | None = None
@@ -177,12 +194,22 @@ class NextItemModel(GenericModel, BatchedGpuModel):
             budget = EngineConfig().arena_bytes(dev) // self.lanes
             self._arena = [DeviceArena(dev, budget, name=f"{type(self).__name__}/lane{i}") for i in range(self.lanes)]
             graph = self._session.graph
-            lanes = [{b: CompiledFunction(graph, {self.feed: ((b, self.seq_len), "INT32")}, self.fetches, dev,
-                                          use_graph=self.use_graph, strict=True, arena=arena)
-                      for b in sorted(self.buckets, reverse=True)} for arena in self._arena]
+            lanes = [{b: self._compile(graph, b, dev, arena) for b in sorted(self.buckets, reverse=True)}
+                     for arena in self._arena]
             self._plans = lanes[0]
             self._runner = PipelinedGpuRunner(lanes, self.feed, lambda p: p.output_tensors(), (self.seq_len,),
                                               torch.int32, depth=self.depth, device=dev)
+
+    def _compile(self, graph, b: int, dev, arena):
+        feeds = {self.feed: ((b, self.seq_len), "INT32")}
+        if not self.pack_tokens:
+            return CompiledFunction(graph, feeds, self.fetches, dev, use_graph=self.use_graph, strict=True, arena=arena)
+        from ...graph.packed import PackedFunction
+
+        full, n = b * self.seq_len, self.PACK_CAPACITIES
+        caps = sorted({min(full, -(-full * i // (n * 64)) * 64) for i in range(1, n + 1)})
+        return PackedFunction(graph, feeds, self.fetches, dev, use_graph=self.use_graph, strict=True, arena=arena,
+                              capacities=caps, pack_causal=True)
 
     def close(self) -> None:
         if self._runner is not None:

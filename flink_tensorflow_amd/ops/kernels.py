@@ -2342,17 +2342,111 @@ def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: 
         _hip().cls_attention_bf16(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), batch, heads, Dh,
                                   float(scale), _stream())
         return out
+    return _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last=False)
+
+
+def _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last: bool):
+    """Host path of ``cls_attention`` / ``last_attention``: the first or last row of each sequence
+    as the only query."""
     cu = cu_seqlens.tolist()
     for b in range(batch):
         a, e = cu[b], cu[b + 1]
         if e <= a:
             out[b] = 0
             continue
-        q = qkv[a, :heads * Dh].float().reshape(heads, 1, Dh)
+        q = qkv[e - 1 if last else a, :heads * Dh].float().reshape(heads, 1, Dh)
         k = qkv[a:e, heads * Dh:2 * heads * Dh].float().reshape(e - a, heads, Dh).transpose(0, 1)
         v = qkv[a:e, 2 * heads * Dh:].float().reshape(e - a, heads, Dh).transpose(0, 1)
         p = torch.softmax((q @ k.transpose(-1, -2)) * scale, -1)
         out[b] = (p @ v).reshape(heads * Dh).to(out.dtype)
+    return out
+
+
+def last_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: int, heads: int,
+                   scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Attention of each packed sequence's LAST token only (row ``cu[b+1] - 1``), the causal twin of
+    ``cls_attention``: the last event may see every key of its sequence, so the final block of a
+    causal transformer whose fetches read the last event needs one query per (sequence, head).
+    Same buffers, head dims and 512-key limit as ``cls_attention`` (``seq`` > 512 raises
+    ``ValueError`` on both paths); an empty sequence gives a zero row and reads nothing."""
+    if seq > CLS_ATTENTION_MAX_SEQ:
+        raise ValueError(f"last_attention: seq {seq} exceeds the {CLS_ATTENTION_MAX_SEQ} keys per sequence the "
+                         "kernel supports")
+    Dh = qkv.shape[1] // (3 * heads)
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * heads * Dh:
+        raise ValueError(f"last_attention: qkv shape {tuple(qkv.shape)} is not [T, 3 * {heads} * Dh]")
+    if cu_seqlens.numel() != batch + 1:
+        raise ValueError("last_attention: cu_seqlens must have B+1 entries")
+    scale = (1.0 / Dh ** 0.5) if scale is None else scale
+    if out is None:
+        out = torch.empty((batch, heads * Dh), dtype=qkv.dtype, device=qkv.device)
+    if qkv.is_cuda:
+        if Dh not in ATTENTION_HEAD_DIMS:
+            raise ValueError(f"last_attention: head dim {Dh} is not one of {ATTENTION_HEAD_DIMS}")
+        _check(qkv, "qkv", device=qkv.device)
+        _check(out, "out", device=qkv.device)
+        _check(cu_seqlens, "cu_seqlens", torch.int32, qkv.device)
+        _hip().last_attention_bf16(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), batch, heads, Dh,
+                                   float(scale), _stream())
+        return out
+    return _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last=True)
+
+
+def packed_rows(cu: torch.Tensor, batch: int, t_cap: int, seq_start: torch.Tensor, last: torch.Tensor) -> None:
+    """Row bookkeeping of a packed batch from its offsets ``cu`` [B+1] (``pack_tokens``):
+    ``seq_start[t]`` = first row of the sequence holding row ``t`` (``t`` itself for a row past
+    ``cu[B]``), ``t < t_cap``; ``last[b] = clamp(cu[b+1] - 1, 0, t_cap - 1)``, the row of sequence
+    b's last token (an empty sequence has none: the value only stays inside the buffer)."""
+    if cu.numel() != batch + 1 or seq_start.numel() != t_cap or last.numel() != batch:
+        raise ValueError("packed_rows: need cu [B+1], seq_start [t_cap], last [B]")
+    if cu.is_cuda:
+        for t, n in ((cu, "cu"), (seq_start, "seq_start"), (last, "last")):
+            _check(t, n, torch.int32, cu.device)
+        _hip().packed_rows(cu.data_ptr(), batch, t_cap, seq_start.data_ptr(), last.data_ptr(), _stream())
+        return
+    c = cu.long()
+    t = torch.arange(t_cap)
+    b = torch.searchsorted(c[1:].contiguous(), t, right=True).clamp(max=batch - 1)  # first b with cu[b+1] > t
+    seq_start.copy_(torch.where(t < c[batch], c[b], t).to(torch.int32))
+    last.copy_((c[1:] - 1).clamp(0, t_cap - 1).to(torch.int32))
+
+
+def packed_causal_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, seq_start: torch.Tensor, batch: int,
+                            heads: int, scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Causal self-attention of a token-packed batch (``kernels/attention_causal_packed.hip``):
+    ``qkv`` [T_cap, 3*H*Dh] bf16 packed rows (on the GPU ``Dh`` is one of ``ATTENTION_HEAD_DIMS``,
+    anything else is a ``ValueError``), ``cu_seqlens`` [B+1] int32, ``seq_start`` [T_cap] int32 from
+    ``packed_rows``.  Query row ``t < cu[B]`` attends key row ``j`` iff ``seq_start[t] <= j <= t``;
+    rows past ``cu[B]`` are neither read nor written.  Returns ctx [T_cap, H*Dh]."""
+    T = qkv.shape[0]
+    Dh = qkv.shape[1] // (3 * heads)
+    if qkv.shape != (T, 3 * heads * Dh):
+        raise ValueError(f"packed_causal_attention: qkv shape {tuple(qkv.shape)} != {(T, 3 * heads * Dh)}")
+    if cu_seqlens.numel() != batch + 1:
+        raise ValueError("packed_causal_attention: cu_seqlens must have B+1 entries")
+    if seq_start.numel() != T:
+        raise ValueError("packed_causal_attention: seq_start must have one entry per row of qkv")
+    scale = (1.0 / Dh ** 0.5) if scale is None else scale
+    if out is None:
+        out = torch.empty((T, heads * Dh), dtype=qkv.dtype, device=qkv.device)
+    if qkv.is_cuda:
+        if Dh not in ATTENTION_HEAD_DIMS:
+            raise ValueError(f"packed_causal_attention: head dim {Dh} is not one of {ATTENTION_HEAD_DIMS}")
+        _check(qkv, "qkv", device=qkv.device)
+        _check(out, "out", device=qkv.device)
+        _check(cu_seqlens, "cu_seqlens", torch.int32, qkv.device)
+        _check(seq_start, "seq_start", torch.int32, qkv.device)
+        _hip().attention_causal_packed_fwd_bf16(qkv.data_ptr(), cu_seqlens.data_ptr(), seq_start.data_ptr(),
+                                                out.data_ptr(), batch, T, heads, Dh, float(scale), _stream())
+        return out
+    n = min(int(cu_seqlens[batch]), T)
+    if n > 0:
+        q, k, v = qkv[:n].float().reshape(n, 3, heads, Dh).permute(1, 2, 0, 3)
+        j = torch.arange(n)
+        ok = (j[None, :] <= j[:, None]) & (j[None, :] >= seq_start[:n].long()[:, None])
+        s = ((q @ k.transpose(-1, -2)) * scale).masked_fill(~ok, float("-inf"))
+        p = torch.softmax(s, -1).nan_to_num(0.0)
+        out[:n] = (p @ v).permute(1, 0, 2).reshape(n, heads * Dh).to(out.dtype)
     return out
 
 
