@@ -141,7 +141,8 @@ def hip_flags() -> list[str]:
 # ones; the older files keep the flags they were measured with.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_FILE_FLAGS = {"retrieve.hip": _NO_PACKED_FP32, "interact.hip": _NO_PACKED_FP32,
-                  "attention_causal.hip": _NO_PACKED_FP32, "attention_causal_packed.hip": _NO_PACKED_FP32}
+                  "attention_causal.hip": _NO_PACKED_FP32, "attention_causal_packed.hip": _NO_PACKED_FP32,
+                  "attention_window.hip": _NO_PACKED_FP32}
 
 
 def build_hip(force: bool = False, verbose: bool = False, jobs: int | None = None) -> Path:

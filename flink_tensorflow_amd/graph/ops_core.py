@@ -398,6 +398,17 @@ def _fill(ctx, node, dims, value):
     return (torch.full(tuple(_ints(dims)), value.item(), dtype=value.dtype, device=ctx.device),)
 
 
+@register("MatrixBandPart")
+def _matrix_band_part(ctx, node, x, lower, upper):
+    """``tf.linalg.band_part``: keeps ``x[..., i, j]`` where ``(lower < 0 or i - j <= lower) and
+    (upper < 0 or j - i <= upper)``, zero elsewhere."""
+    lo, up = int(lower.item()), int(upper.item())
+    d = torch.arange(x.shape[-2], device=x.device)[:, None] - torch.arange(x.shape[-1], device=x.device)[None, :]
+    keep = ((d <= lo) if lo >= 0 else torch.ones_like(d, dtype=torch.bool)) & \
+           ((-d <= up) if up >= 0 else torch.ones_like(d, dtype=torch.bool))
+    return (torch.where(keep, x, torch.zeros_like(x)),)
+
+
 @register("Range")
 def _range(ctx, node, start, limit, delta):
     dt = node.attr("Tidx", DataType.INT32)

@@ -19,11 +19,15 @@ Google's ``modeling.py``) arrives as decomposed ops.  Before lowering, the compi
   the key-mask chain above (``Cast`` / ``ExpandDims`` / ``Reshape`` over the fed mask or
   ``NotEqual(ids, 0)``) and ``C`` a constant with trailing dims ``[S, S]``, every other dim 1,
   equal to the lower-triangular ones matrix exactly -> the fused QKV ``gemm`` + ONE
-  ``causal_attention`` launch (``kernels/attention_causal.hip``, ``S <= 2048``).  Any other
-  constant (upper or strict lower triangle, a band, a shifted diagonal, values other than 0/1)
-  matches nothing and the ``BatchMatMul`` / ``Softmax`` chain stays glue, as do a causal mask
-  with no key mask and one given as a second adder.  Causal graphs token-pack on request only
-  (``pack_causal``, below);
+  ``causal_attention`` launch (``kernels/attention_causal.hip``, ``S <= 2048``);
+* sliding-window causal self-attention — the causal chain whose ``C`` is exactly the band
+  ``tril AND (i - j < W)`` for one ``1 <= W < S`` (what ``tf.linalg.band_part(ones, W - 1, 0)``
+  folds to) -> the fused QKV ``gemm`` + ONE ``window_attention`` launch
+  (``kernels/attention_window.hip``, ``S <= 8192``, cost S * W); ``W >= S`` is the tril above.
+  Any other constant (upper or strict lower triangle, a band with a hole or off the diagonal, a
+  shifted diagonal, values other than 0/1) matches nothing and the ``BatchMatMul`` / ``Softmax``
+  chain stays glue, as do a causal mask with no key mask and one given as a second adder.
+  Causal graphs token-pack on request only (``pack_causal``, below);
 * embeddings without a token-type row (``GatherV2 + positions -> layer_norm``, an item or event
   embedding) take the same ``embed_layernorm`` launch with a zero type row;
 * GELU — BERT's tanh form after a ``MatMul+BiasAdd`` -> the GEMM's GELU epilogue;
@@ -58,7 +62,9 @@ region through the same walk: the final block's attention becomes ``last_attenti
 sequence; ``S <= 512``, above that no region forms and the slice gathers behind the full step) and
 everything after it runs on B rows.  First- and last-token slices in one graph, and a slice of any
 other position, stay a ``CompileError``; a first-token region never reaches through a causal group
-(its first row sees itself only).
+(its first row sees itself only).  Windowed groups pack the same way: ``packed_rows`` writes the
+windowed starts ``max(seq_start[t], t - W + 1)`` and ``last_attention`` reads the last ``W`` rows (the
+region forms when ``min(S, W) <= 512``); all causal groups of a packed graph must share one window.
 """
 from __future__ import annotations
 
@@ -232,6 +238,7 @@ class TransformerLowering:
             members |= {mm.name, ba.name, rs.name, tr.name}
         self._add_group({"kind": "attn", "x": br[0][0], "branches": [b[1:] for b in br], "scale": scale_src,
                          "mask": mask_src, "mask_chain": chain, "causal": tril_src is not None, "tril": tril_src,
+                         "window": _band_window(self._const_of(tril_src)) if tril_src is not None else None,
                          "perm": tr_o.inputs[1], "out": rs_o.name, "members": members})
 
     def _mask_leaf(self, src):
@@ -240,7 +247,8 @@ class TransformerLowering:
         ``NotEqual(ids, 0)`` of the fed ids — in both cases "key j is padding" is
         ``leaf[b, j] == 0``, the attention kernel's pad test.  The causal form has one more link
         right under the ``Sub``: ``(1 - Mul(A, C)) * c`` (either operand order) with ``A`` the key
-        mask chain above and ``C`` the lower-triangular ones constant (``_is_tril``)."""
+        mask chain above and ``C`` the lower-triangular ones constant (``_is_tril``) or a band of it
+        (``_band_window``)."""
         none = (None, None, None)
         chain, cur, tril = [], self._node(src), None
         for i in range(7):
@@ -264,7 +272,10 @@ class TransformerLowering:
             if i == 1 and nxt.op == "Mul":  # the causal link: M = A * tril
                 a_src = [s for s in nxt.inputs if not self._is_const_node(s)]
                 c_src = [s for s in nxt.inputs if self._is_const_node(s)]
-                if len(a_src) != 1 or len(c_src) != 1 or not _is_tril(self._const_of(c_src[0])):
+                if len(a_src) != 1 or len(c_src) != 1:
+                    return none
+                c = self._const_of(c_src[0])
+                if not _is_tril(c) and _band_window(c) is None:
                     return none
                 chain.append(nxt.name)
                 tril = c_src[0]
@@ -334,6 +345,10 @@ class TransformerLowering:
         causal = any(g.get("causal") for g in attns)
         if causal and not self.pack_causal:
             raise CompileError("token packing of causal attention is opt-in (pack_causal=True)")
+        windows = {g.get("window") for g in attns if g.get("causal")}
+        if len(windows) > 1:  # packed_rows writes ONE set of starts for the graph
+            raise CompileError(f"token packing needs one attention window for all causal groups, got {windows}")
+        window = next(iter(windows), None) or 0
         ids_src = embs[0]["ids"]
         feed = f"{ids_src[0]}:{ids_src[1]}"  # feed names are normalised to ``node:index``
         if feed not in self.feed_names:
@@ -350,9 +365,10 @@ class TransformerLowering:
             raise CompileError(f"token capacity {T} outside (0, {B * S}]")
         # "token": which row of a sequence the one-token slices read ("first" / "last" / None); "one":
         # that row's index per sequence (pack_tokens' ``cls`` or packed_rows' ``last``); "seq_start":
-        # packed_rows' per-row sequence starts, present when a causal group or a last-token slice needs them
+        # packed_rows' per-row sequence starts, present when a causal group or a last-token slice needs them;
+        # "window": the causal groups' common attention window (0: none), which those starts carry
         self._pack = {"ids": ids_src, "feed": feed, "B": B, "S": S, "T": T, "pad": 0, "cu": None, "one": None,
-                      "token": None, "seq_start": None, "rows": causal}
+                      "token": None, "seq_start": None, "rows": causal, "window": window}
         # one-token-only region: nodes whose every consumer is in the region or is the one-token
         # slice (the pooler's first token, or a next-item head's last event; reverse topological
         # order: consumers first)
@@ -367,7 +383,7 @@ class TransformerLowering:
             if not self.pack_causal:
                 raise CompileError("a last-token slice of packed rows is opt-in (pack_causal=True)")
             self._pack["rows"] = True
-            if S > K.CLS_ATTENTION_MAX_SEQ:  # no one-query kernel: the slice is a gather behind the full step
+            if (min(S, window) if window else S) > K.CLS_ATTENTION_MAX_SEQ:  # no one-query kernel: the slice is a gather behind the full step
                 return
         # the first row of a causal sequence sees itself only: no first-token region through causal attention
         attn_out = {g["out"]: g for g in attns if token == "last" or not g.get("causal")}
@@ -564,7 +580,7 @@ class TransformerLowering:
                     pk["one"] = last
 
                 def run_rows(cu=cu, start=start, last=last):
-                    K.packed_rows(cu.buf, B, T, start.buf, last.buf)
+                    K.packed_rows(cu.buf, B, T, start.buf, last.buf, window=pk["window"])
 
                 self._emit(grp["out"] + "/packed_rows", "packed_rows", run_rows, [cu], [start, last])
             out = self._new((T, D))
@@ -627,8 +643,14 @@ class TransformerLowering:
                 any(w.shape != (H, Din) for w in ws):
             return False
         causal = grp.get("causal", False)
-        if causal and ((pk is not None and pk["seq_start"] is None) or S > K.CAUSAL_ATTENTION_MAX_SEQ
-                       or not _is_tril(self._const_of(grp["tril"]), S)):  # the folded constant, checked again
+        window = grp.get("window") if causal else None
+        if causal and pk is not None and (pk["seq_start"] is None or pk["window"] != (window or 0)):
+            return False
+        if causal and window is None and (S > K.CAUSAL_ATTENTION_MAX_SEQ
+                                          or not _is_tril(self._const_of(grp["tril"]), S)):  # the folded constant,
+            return False                                                                    # checked again
+        if window is not None and (S > K.WINDOW_ATTENTION_MAX_SEQ
+                                   or _band_window(self._const_of(grp["tril"]), S) != window):
             return False
         w_qkv = self._dev(torch.cat(ws, 0), torch.bfloat16)
         b_qkv = self._dev(torch.cat(bs, 0), torch.float32)
@@ -656,7 +678,9 @@ class TransformerLowering:
             cu, start = pk["cu"], pk["seq_start"]
 
             def run_attn(qkv=qkv, ctx=ctx, cu=cu):
-                if cls_only:  # one query per sequence (the fetches read nothing else): its first or last row
+                if cls_only and window:  # the last row over its window (a windowed group is causal: never first-token)
+                    K.last_attention(qkv.buf, cu.buf, B, S, nh, scale=sc, out=ctx.buf, window=window)
+                elif cls_only:  # one query per sequence (the fetches read nothing else): its first or last row
                     one(qkv.buf, cu.buf, B, S, nh, scale=sc, out=ctx.buf)
                 elif causal:
                     K.packed_causal_attention(qkv.buf, cu.buf, start.buf, B, nh, scale=sc, out=ctx.buf)
@@ -667,12 +691,14 @@ class TransformerLowering:
         else:
             def run_attn(qkv=qkv, ctx=ctx, mask=mask):
                 K.attention(qkv.buf, _view(mask).reshape(-1), B, S, nh, pad_id=0, scale=sc, out=ctx.buf,
-                            causal=causal)
+                            causal=causal, window=window)
 
         if cls_only:
             kind = "last_attention" if one is K.last_attention else "cls_attention"
+        elif causal and pk is None:
+            kind = "window_attention" if window is not None else "causal_attention"
         elif causal:
-            kind = "packed_causal_attention" if pk is not None else "causal_attention"
+            kind = "packed_causal_attention"
         else:
             kind = "attention"
         ins = [qkv, mask] + ([pk["seq_start"]] if kind == "packed_causal_attention" else [])
@@ -800,3 +826,21 @@ def _is_tril(c, S: int | None = None) -> bool:
         return False
     n = c.shape[-1]
     return (S is None or n == S) and torch.equal(c.reshape(n, n).double(), torch.ones(n, n, dtype=torch.float64).tril())
+
+
+def _band_window(c, S: int | None = None) -> int | None:
+    """W when ``c`` is the sliding-window causal constant: trailing dims ``[S, S]``, every other dim
+    1, and exactly ``tril AND (query - key < W)`` for one ``1 <= W < S`` (1 where ``i - W < j <= i``,
+    0 elsewhere); None for anything else, the full tril (``W >= S``, ``_is_tril``) included."""
+    if c is None or c.dim() < 2 or c.shape[-1] != c.shape[-2] or c.numel() != c.shape[-1] ** 2:
+        return None
+    n = c.shape[-1]
+    if n < 2 or (S is not None and n != S):
+        return None
+    m = c.reshape(n, n).double()
+    ones = float(m[-1].sum())  # the last row holds W ones when c is a band
+    if not 1 <= ones < n or ones != int(ones):
+        return None
+    w = int(ones)
+    band = torch.ones(n, n, dtype=torch.float64).tril().triu(-(w - 1))
+    return w if torch.equal(m, band) else None

@@ -412,17 +412,21 @@ __global__ __launch_bounds__(1024) void pack_tokens_kernel(const int* __restrict
 // LAST picks the query row at compile time: false is the sequence's first row (cls_attention),
 // true its last one, row cu[b+1] - 1 (last_attention: the final block of a causal transformer
 // whose fetches read the last event only; that row may attend every key of its sequence, so the
-// causal mask is vacuous and the kernel is the same).
+// causal mask is vacuous and the kernel is the same).  With LAST and window > 0 (sliding-window
+// causal attention) the keys are the sequence's last ``window`` rows, max(cu[b], cu[b+1] - window)
+// .. cu[b+1] - 1, and the 512-key limit applies to those; the first-token kernels ignore ``window``.
 template <bool LAST>
 __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restrict__ qkv, const int* __restrict__ cu,
-                                                            bf16* __restrict__ out, int B, int H, float scale_log2e) {
+                                                            bf16* __restrict__ out, int B, int H, float scale_log2e,
+                                                            int window) {
   __shared__ float probs[4][512];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int bh = blockIdx.x * 4 + wave;
   if (bh >= B * H) return;  // wave-uniform; no block barrier below
   const int b = bh / H, h = bh % H;
   const int ld = 3 * H * D;
-  const int t0 = cu[b];
+  int t0 = cu[b];
+  if (LAST && window > 0) t0 = max(t0, cu[b + 1] - window);
   const int n = min(cu[b + 1] - t0, 512);
   if (n <= 0) {  // empty sequence: a zero row, and row t0 (possibly one past the batch) is not read
     out[(size_t)b * H * D + h * D + lane] = f2bf(0.f);
@@ -477,7 +481,7 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const bf16* __restri
 template <int DH, bool LAST>
 __global__ __launch_bounds__(256) void cls_attention_hd_kernel(const bf16* __restrict__ qkv,
                                                                const int* __restrict__ cu, bf16* __restrict__ out,
-                                                               int B, int H, float scale_log2e) {
+                                                               int B, int H, float scale_log2e, int window) {
   static_assert(DH == 32 || DH == 128, "64 is cls_attention_kernel");
   typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
   __shared__ float probs[4][512];
@@ -486,7 +490,8 @@ __global__ __launch_bounds__(256) void cls_attention_hd_kernel(const bf16* __res
   if (bh >= B * H) return;  // wave-uniform; no block barrier below
   const int b = bh / H, h = bh % H;
   const int HD = H * DH, ld = 3 * HD;
-  const int t0 = cu[b];
+  int t0 = cu[b];
+  if (LAST && window > 0) t0 = max(t0, cu[b + 1] - window);  // the last ``window`` rows only
   const int n = min(cu[b + 1] - t0, 512);
   bf16* orow = out + (size_t)b * HD + h * DH;
   const bf16* base = qkv + (size_t)t0 * ld + h * DH;  // Q of the sequence's first row; K, V lie HD, 2 HD further
@@ -620,7 +625,9 @@ void embed_ln_bf16(uintptr_t ids, uintptr_t tt, uintptr_t pos_ids, uintptr_t wor
 namespace {
 
 template <bool LAST>
-void launch_one_query(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale, uintptr_t stream) {
+void launch_one_query(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale, uintptr_t stream,
+                      int window = 0) {
+  if (window < 0) throw std::invalid_argument("last_attention: window must be >= 1, or 0 for none");
   if (Dh != 32 && Dh != 64 && Dh != 128) throw std::invalid_argument("cls_attention: head dim must be 32, 64 or 128");
   if (B <= 0 || H <= 0 || !cu) throw std::invalid_argument("cls_attention: empty problem / no cu_seqlens");
   // 16-B loads of q and k; the output row is stored 2 B per lane (4 B at 128: two columns a lane)
@@ -632,7 +639,7 @@ void launch_one_query(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, 
                                 : cls_attention_kernel<LAST>;
   hipLaunchKernelGGL(kern, dim3((waves + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const bf16*>(qkv), reinterpret_cast<const int*>(cu), reinterpret_cast<bf16*>(out),
-                     B, H, scale * 1.4426950408889634f);
+                     B, H, scale * 1.4426950408889634f, window);
   FTM_CHECK_LAUNCH();
 }
 
@@ -643,15 +650,17 @@ void cls_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H
   launch_one_query<false>(qkv, cu, out, B, H, Dh, scale, stream);
 }
 
-// the same kernels with each sequence's LAST row as the query
+// the same kernels with each sequence's LAST row as the query, over its last ``window`` rows (0: all)
 void last_attention_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t out, int B, int H, int Dh, float scale,
-                         uintptr_t stream) {
-  launch_one_query<true>(qkv, cu, out, B, H, Dh, scale, stream);
+                         uintptr_t stream, int window) {
+  launch_one_query<true>(qkv, cu, out, B, H, Dh, scale, stream, window);
 }
 
 void register_attention(pybind11::module_& m) {
   m.def("cls_attention_bf16", &cls_attention_bf16);
-  m.def("last_attention_bf16", &last_attention_bf16);
+  namespace py = pybind11;  // ``window`` is optional and last: the eight-argument call is unchanged
+  m.def("last_attention_bf16", &last_attention_bf16, py::arg("qkv"), py::arg("cu"), py::arg("out"), py::arg("B"),
+        py::arg("H"), py::arg("Dh"), py::arg("scale"), py::arg("stream"), py::arg("window") = 0);
   m.def("attention_fwd_bf16", &attention_fwd_bf16);
   m.def("embed_ln_bf16", &embed_ln_bf16);
   m.def("pack_tokens", &pack_tokens);

@@ -191,9 +191,12 @@ __global__ __launch_bounds__(NTH) void attention_causal_packed_kernel(const bf16
 // last token, clamped into [0, T_cap - 1] (an empty sequence has none; its value is not used as a
 // query by last_attention, only as a gather index that must stay inside the buffer).  Thread t
 // finds the first b with cu[b + 1] > t by bisection (cu is non-decreasing; empty sequences share a
-// start and are passed over).
+// start and are passed over).  window > 0 (sliding-window causal attention): row t sees its last
+// ``window`` rows only, seq_start[t] = max(cu[b], t - window + 1), which is still non-decreasing
+// along the stream, so the attention kernel above serves it unchanged.
 __global__ __launch_bounds__(256) void packed_rows_kernel(const int* __restrict__ cu, int B, int T_cap,
-                                                          int* __restrict__ seq_start, int* __restrict__ last) {
+                                                          int* __restrict__ seq_start, int* __restrict__ last,
+                                                          int window) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t < B) last[t] = min(max(cu[t + 1] - 1, 0), T_cap - 1);
   if (t >= T_cap) return;
@@ -206,6 +209,7 @@ __global__ __launch_bounds__(256) void packed_rows_kernel(const int* __restrict_
       else lo = mid + 1;
     }
     v = cu[lo];
+    if (window > 0) v = max(v, t - window + 1);
   }
   seq_start[t] = v;
 }
@@ -234,16 +238,19 @@ void attention_causal_packed_fwd_bf16(uintptr_t qkv, uintptr_t cu, uintptr_t seq
   FTM_CHECK_LAUNCH();
 }
 
-void packed_rows(uintptr_t cu, int B, int T_cap, uintptr_t seq_start, uintptr_t last, uintptr_t stream) {
+void packed_rows(uintptr_t cu, int B, int T_cap, uintptr_t seq_start, uintptr_t last, uintptr_t stream, int window) {
   if (B <= 0 || T_cap <= 0 || !cu || !seq_start || !last) throw std::invalid_argument("packed_rows: empty problem");
+  if (window < 0) throw std::invalid_argument("packed_rows: window must be >= 1, or 0 for none");
   const int n = T_cap > B ? T_cap : B;
   hipLaunchKernelGGL(packed_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int*>(cu), B, T_cap,
-                     reinterpret_cast<int*>(seq_start), reinterpret_cast<int*>(last));
+                     reinterpret_cast<int*>(seq_start), reinterpret_cast<int*>(last), window);
   FTM_CHECK_LAUNCH();
 }
 
 void register_attention_causal_packed(pybind11::module_& m) {
   m.def("attention_causal_packed_fwd_bf16", &attention_causal_packed_fwd_bf16);
-  m.def("packed_rows", &packed_rows);
+  namespace py = pybind11;  // ``window`` is optional and last: the six-argument call is unchanged
+  m.def("packed_rows", &packed_rows, py::arg("cu"), py::arg("B"), py::arg("T_cap"), py::arg("seq_start"),
+        py::arg("last"), py::arg("stream"), py::arg("window") = 0);
 }

@@ -17,6 +17,7 @@ void register_fp8(pybind11::module_& m);
 void register_attention(pybind11::module_& m);
 void register_attention_causal(pybind11::module_& m);
 void register_attention_causal_packed(pybind11::module_& m);
+void register_attention_window(pybind11::module_& m);
 void register_dconv(pybind11::module_& m);
 void register_elementwise(pybind11::module_& m);
 void register_conv3x3c64(pybind11::module_& m);
@@ -52,6 +53,7 @@ PYBIND11_MODULE(_hip, m) {
   register_attention(m);
   register_attention_causal(m);
   register_attention_causal_packed(m);
+  register_attention_window(m);
   register_dconv(m);
   register_elementwise(m);
   register_conv3x3c64(m);

@@ -21,10 +21,16 @@ table; ``item_bias[0]`` is a large negative constant so the pad id is never reco
 hidden size is one of 64, 128, 192, 256 (``retrieve``'s ``D <= 256``) and equals ``head_dim * heads``
 with 32-, 64- (the default) or 128-wide heads: SASRec / BERT4Rec sizes such as hidden 64 with 2 heads.
 
+``NextItemConfig.window = W`` makes the attention local: the mask constant is the band ``i - W < j
+<= i`` of the tril, each block's attention lowers to one ``window_attention`` step
+(``kernels/attention_window.hip``) whose cost grows with ``S * W`` instead of ``S * S``, and the
+history may be up to 8192 events long (2048 without a window).  ``W >= seq_len`` is the causal model.
+
 ``NextItemModel(pack_tokens=True)`` serves the same graph padding-free (``graph/packed.py`` with
 ``pack_causal=True``): ``pack_tokens`` + ``packed_rows`` + ``embed_ln`` at each event's own position,
 every block on the real events only (``packed_causal_attention``), and the last block after its QKV
 projection on one row per session (``last_attention``, then projections and LayerNorms on B rows).
+With a window, ``packed_rows`` writes the windowed starts and ``last_attention`` reads the last W events.
 
 Tensor names: ``item_ids`` (int32 [N, S]), ``scores``, ``top_k`` (``top_k:0`` scores, ``top_k:1``
 item ids).
@@ -57,8 +63,11 @@ class NextItemConfig:
     intermediate: int = 512
     eps: float = 1e-12
     head_dim: int = 64       # 32, 64 or 128: the widths the attention kernels are built for
+    window: int | None = None  # W: each event sees its last W events only (itself included); None: all before it
 
     def __post_init__(self):
+        if self.window is not None and self.window < 1:
+            raise ValueError("NextItemConfig: window must be >= 1")
         if self.head_dim not in (32, 64, 128):
             raise ValueError("NextItemConfig: head_dim must be 32, 64 or 128")
         if self.hidden not in (64, 128, 192, 256) or self.hidden != self.head_dim * self.heads:
@@ -91,11 +100,12 @@ def init_next_item_weights(cfg: NextItemConfig, seq_len: int, seed: int = 0) -> 
 
 def next_item_graph_def(cfg: NextItemConfig | None = None, seq_len: int = 64, k: int = 10, seed: int = 0,
                         weights: dict | None = None, causal_const: np.ndarray | None = None,
-                        query_pos: int | None = None) -> GraphDef:
+                        query_pos: int | None = None, band_part: bool = False) -> GraphDef:
     """The frozen graph on ``[B, seq_len]`` ids (B dynamic) with ``k`` recommendations per record.
     ``weights`` replaces ``init_next_item_weights(cfg, seq_len, seed)``; ``causal_const`` replaces
-    the ``[1, 1, S, S]`` lower-triangular ones constant of the attention mask, ``query_pos`` the
-    position ``S - 1`` whose hidden state is the query."""
+    the ``[1, 1, S, S]`` lower-triangular ones constant of the attention mask (with ``cfg.window``:
+    its band), ``query_pos`` the position ``S - 1`` whose hidden state is the query; ``band_part``
+    writes that constant as a ``MatrixBandPart`` node over ones instead."""
     cfg = cfg or NextItemConfig()
     w = weights if weights is not None else init_next_item_weights(cfg, seq_len, seed)
     S, H = seq_len, cfg.hidden
@@ -121,8 +131,19 @@ def next_item_graph_def(cfg: NextItemConfig | None = None, seq_len: int = 64, k:
                                   name="next_item/encoder/ExpandDims", T=DataType.FLOAT, Tdim=DataType.INT32),
                              _c(b, "next_item/encoder/ExpandDims_1/dim", np.int32(1))],
               name="next_item/encoder/ExpandDims_1", T=DataType.FLOAT, Tdim=DataType.INT32)
-    tril = np.tril(np.ones((S, S), np.float32))[None, None] if causal_const is None else causal_const
-    m4 = b.mul(m4, _c(b, "next_item/encoder/causal_mask", np.asarray(tril, np.float32)), name="next_item/encoder/mul")
+    tril = np.tril(np.ones((S, S), np.float32))
+    if cfg.window is not None:  # the band i - W < j <= i; W >= S leaves the tril
+        tril = np.triu(tril, -(cfg.window - 1))
+    tril = tril[None, None] if causal_const is None else causal_const
+    if band_part:  # the mask as tf.linalg.band_part(ones, W - 1, 0) leaves it in a frozen graph (-1: the tril)
+        lower = -1 if cfg.window is None else cfg.window - 1
+        cm = b.op("MatrixBandPart", [_c(b, "next_item/encoder/ones", np.ones((1, 1, S, S), np.float32)),
+                                     _c(b, "next_item/encoder/band_part/num_lower", np.int64(lower)),
+                                     _c(b, "next_item/encoder/band_part/num_upper", np.int64(0))],
+                  name="next_item/encoder/causal_mask", T=DataType.FLOAT, Tindex=DataType.INT64)
+    else:
+        cm = _c(b, "next_item/encoder/causal_mask", np.asarray(tril, np.float32))
+    m4 = b.mul(m4, cm, name="next_item/encoder/mul")
     one_minus = b.sub(_c(b, "next_item/encoder/sub/x", np.float32(1.0)), m4, name="next_item/encoder/sub")
     adder = b.mul(one_minus, _c(b, "next_item/encoder/mul_1/y", np.float32(-10000.0)), name="next_item/encoder/mul_1")
     x2 = b.reshape(x, [-1, H], name="next_item/encoder/Reshape")

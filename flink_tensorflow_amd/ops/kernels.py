@@ -2247,12 +2247,14 @@ def softmax_topk(logits: torch.Tensor, k: int, want_probs: bool = False, vals=No
 
 # ------------------------------------------------------------------------------ attention
 CAUSAL_ATTENTION_MAX_SEQ = 2048  # longest sequence of the causal attention kernel
+WINDOW_ATTENTION_MAX_SEQ = 8192  # longest sequence of the windowed causal kernel: a choice, its walk is bounded by W
 ATTENTION_HEAD_DIMS = (32, 64, 128)  # head widths the attention kernels are built for
 
 
 def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int, heads: int, pad_id: int = 0,
               scale: float | None = None, out: torch.Tensor | None = None,
-              cu_seqlens: torch.Tensor | None = None, causal: bool = False) -> torch.Tensor:
+              cu_seqlens: torch.Tensor | None = None, causal: bool = False,
+              window: int | None = None) -> torch.Tensor:
     """Multi-head self-attention over the fused QKV projection output.
 
     Padded batch: ``qkv`` [B*S, 3*H*Dh] bf16 (Q|K|V blocks, head h at h*Dh; on the GPU ``Dh`` is
@@ -2262,11 +2264,17 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
     ``cu[b]:cu[b+1]`` of ``qkv``, no padding; rows past ``cu[B]`` are left untouched.
     ``causal`` (padded batch only, ``1 <= S <= 2048``): query i attends key j iff ``j <= i`` and key
     j is not padding, on ``kernels/attention_causal.hip``; a query with no admissible key gets a
-    zero row.  Returns ctx [rows, H*Dh]."""
+    zero row.  ``window`` = W (with ``causal`` only, ``W >= 1``, ``1 <= S <= 8192``): sliding-window
+    causal attention, query i attends key j iff ``i - W < j <= i`` and key j is not padding, on
+    ``kernels/attention_window.hip``, whose key walk per query block is bounded by W whatever S
+    is; ``W >= S`` is the causal result.  Returns ctx [rows, H*Dh]."""
+    if window is not None and (not causal or window < 1):
+        raise ValueError("attention: window needs causal=True and window >= 1")
     if causal and cu_seqlens is not None:
         raise ValueError("attention: causal attention of a packed batch (cu_seqlens) is not supported")
-    if causal and not 1 <= seq <= CAUSAL_ATTENTION_MAX_SEQ:  # the kernel's envelope, on the host path too
-        raise ValueError(f"attention: causal attention needs 1 <= seq <= {CAUSAL_ATTENTION_MAX_SEQ}, got {seq}")
+    max_seq = CAUSAL_ATTENTION_MAX_SEQ if window is None else WINDOW_ATTENTION_MAX_SEQ
+    if causal and not 1 <= seq <= max_seq:  # the kernel's envelope, on the host path too
+        raise ValueError(f"attention: causal attention needs 1 <= seq <= {max_seq}, got {seq}")
     T = qkv.shape[0] if cu_seqlens is not None else batch * seq
     Dh = qkv.shape[1] // (3 * heads)
     if qkv.shape != (T, 3 * heads * Dh):
@@ -2287,6 +2295,10 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
             _check(cu_seqlens, "cu_seqlens", torch.int32, qkv.device)
         else:
             _check(ids, "ids", torch.int32, qkv.device)
+        if window is not None:
+            _hip().attention_window_fwd_bf16(qkv.data_ptr(), ids.data_ptr(), out.data_ptr(), batch, seq, heads, Dh,
+                                             min(int(window), seq), pad_id, float(scale), _stream())
+            return out
         if causal:
             _hip().attention_causal_fwd_bf16(qkv.data_ptr(), ids.data_ptr(), out.data_ptr(), batch, seq, heads, Dh,
                                              pad_id, float(scale), _stream())
@@ -2308,6 +2320,8 @@ def attention(qkv: torch.Tensor, ids: torch.Tensor | None, batch: int, seq: int,
     mask = (ids.reshape(batch, 1, 1, seq) == pad_id)
     if causal:  # key j > query i
         mask = mask | torch.ones(seq, seq, dtype=torch.bool, device=ids.device).triu(1)
+    if window is not None and window < seq:  # key j <= query i - W
+        mask = mask | torch.ones(seq, seq, dtype=torch.bool, device=ids.device).tril(-int(window))
     s = s.masked_fill(mask, float("-inf"))
     p = torch.softmax(s, -1).nan_to_num(0.0)
     o = (p @ v).permute(0, 2, 1, 3).reshape(T, heads * Dh)
@@ -2345,12 +2359,14 @@ def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: 
     return _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last=False)
 
 
-def _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last: bool):
+def _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last: bool, window: int = 0):
     """Host path of ``cls_attention`` / ``last_attention``: the first or last row of each sequence
-    as the only query."""
+    as the only query (``window`` > 0: over the sequence's last ``window`` rows)."""
     cu = cu_seqlens.tolist()
     for b in range(batch):
         a, e = cu[b], cu[b + 1]
+        if window > 0:
+            a = max(a, e - window)
         if e <= a:
             out[b] = 0
             continue
@@ -2363,13 +2379,17 @@ def _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last: bool):
 
 
 def last_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq: int, heads: int,
-                   scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+                   scale: float | None = None, out: torch.Tensor | None = None, window: int = 0) -> torch.Tensor:
     """Attention of each packed sequence's LAST token only (row ``cu[b+1] - 1``), the causal twin of
     ``cls_attention``: the last event may see every key of its sequence, so the final block of a
     causal transformer whose fetches read the last event needs one query per (sequence, head).
     Same buffers, head dims and 512-key limit as ``cls_attention`` (``seq`` > 512 raises
-    ``ValueError`` on both paths); an empty sequence gives a zero row and reads nothing."""
-    if seq > CLS_ATTENTION_MAX_SEQ:
+    ``ValueError`` on both paths); an empty sequence gives a zero row and reads nothing.
+    ``window`` = W > 0 (sliding-window causal attention): the keys are rows ``max(cu[b], cu[b+1] - W)
+    .. cu[b+1] - 1`` and the 512-key limit applies to ``min(seq, W)``; 0 is no window."""
+    if window < 0:
+        raise ValueError("last_attention: window must be >= 1, or 0 for none")
+    if (min(seq, window) if window else seq) > CLS_ATTENTION_MAX_SEQ:
         raise ValueError(f"last_attention: seq {seq} exceeds the {CLS_ATTENTION_MAX_SEQ} keys per sequence the "
                          "kernel supports")
     Dh = qkv.shape[1] // (3 * heads)
@@ -2387,27 +2407,37 @@ def last_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, batch: int, seq:
         _check(out, "out", device=qkv.device)
         _check(cu_seqlens, "cu_seqlens", torch.int32, qkv.device)
         _hip().last_attention_bf16(qkv.data_ptr(), cu_seqlens.data_ptr(), out.data_ptr(), batch, heads, Dh,
-                                   float(scale), _stream())
+                                   float(scale), _stream(), int(window))
         return out
-    return _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last=True)
+    return _one_query_host(qkv, cu_seqlens, batch, heads, Dh, scale, out, last=True, window=int(window))
 
 
-def packed_rows(cu: torch.Tensor, batch: int, t_cap: int, seq_start: torch.Tensor, last: torch.Tensor) -> None:
+def packed_rows(cu: torch.Tensor, batch: int, t_cap: int, seq_start: torch.Tensor, last: torch.Tensor,
+                window: int = 0) -> None:
     """Row bookkeeping of a packed batch from its offsets ``cu`` [B+1] (``pack_tokens``):
     ``seq_start[t]`` = first row of the sequence holding row ``t`` (``t`` itself for a row past
     ``cu[B]``), ``t < t_cap``; ``last[b] = clamp(cu[b+1] - 1, 0, t_cap - 1)``, the row of sequence
-    b's last token (an empty sequence has none: the value only stays inside the buffer)."""
+    b's last token (an empty sequence has none: the value only stays inside the buffer).
+    ``window`` = W > 0 (sliding-window causal attention): ``seq_start[t] = max(that, t - W + 1)``,
+    the first row query ``t`` still sees; the starts stay non-decreasing, which is all
+    ``packed_causal_attention`` asks of them.  0 is no window."""
     if cu.numel() != batch + 1 or seq_start.numel() != t_cap or last.numel() != batch:
         raise ValueError("packed_rows: need cu [B+1], seq_start [t_cap], last [B]")
+    if window < 0:
+        raise ValueError("packed_rows: window must be >= 1, or 0 for none")
     if cu.is_cuda:
         for t, n in ((cu, "cu"), (seq_start, "seq_start"), (last, "last")):
             _check(t, n, torch.int32, cu.device)
-        _hip().packed_rows(cu.data_ptr(), batch, t_cap, seq_start.data_ptr(), last.data_ptr(), _stream())
+        _hip().packed_rows(cu.data_ptr(), batch, t_cap, seq_start.data_ptr(), last.data_ptr(), _stream(),
+                           int(window))
         return
     c = cu.long()
     t = torch.arange(t_cap)
     b = torch.searchsorted(c[1:].contiguous(), t, right=True).clamp(max=batch - 1)  # first b with cu[b+1] > t
-    seq_start.copy_(torch.where(t < c[batch], c[b], t).to(torch.int32))
+    start = torch.where(t < c[batch], c[b], t)
+    if window > 0:
+        start = torch.maximum(start, t - int(window) + 1)
+    seq_start.copy_(start.to(torch.int32))
     last.copy_((c[1:] - 1).clamp(0, t_cap - 1).to(torch.int32))
 
 
