@@ -20,7 +20,12 @@ lookups as ``embed`` steps and the rest as glue.
 
 ``--wide``: B = 32768 at ``F x D`` = 26 x 256, 48 x 128 and 48 x 256 (the other kernel instantiations).
 
+``--tables fp8``: the same shapes with 8-bit tables (``kernels/interact_fp8.hip``) against the bf16 step on tables of
+the same values and the same ids, each with its share of its own roof (a row is ``D + 1`` bytes instead of ``2 D``)
+and whether both outputs have the same bits.
+
     python bench/interact_probe.py --rounds 5 --wide --model
+    python bench/interact_probe.py --rounds 5 --wide --tables fp8
 """
 import argparse
 import json
@@ -106,6 +111,55 @@ def step(table, B, F, D, rows, dist, dev, window_us, rounds):
                       "max_abs_diff": diff}), flush=True)
 
 
+def fp8_tables(F, rows, D, dev):
+    """Random 8-bit tables built on the device (finite codes, row exponents in -8..-4) and the bf16 table they stand
+    for, one field at a time: ``(codes, exps, bf16 table)``."""
+    g = torch.Generator(device=dev).manual_seed(F + D)
+    finite = torch.tensor([c for c in range(256) if c & 0x7F != 0x7F], dtype=torch.uint8)
+    value = K.dequantize_table_fp8(finite[:, None].expand(254, 16).contiguous(), torch.zeros(254, dtype=torch.int8))[:, 0].to(dev)
+    codes = torch.empty((F * rows, D), dtype=torch.uint8, device=dev)
+    exps = torch.randint(-8, -3, (F * rows,), device=dev, generator=g, dtype=torch.int8)
+    table = torch.empty((F * rows, D), dtype=BF, device=dev)
+    for f in range(F):
+        s = slice(f * rows, (f + 1) * rows)
+        pick = torch.randint(0, 254, (rows, D), device=dev, generator=g)
+        codes[s] = finite.to(dev)[pick]
+        table[s] = value[pick] * torch.exp2(exps[s].float()).to(BF)[:, None]  # a power of two: exact
+        del pick
+    return codes, exps, table
+
+
+def step_fp8(tables, B, F, D, rows, dist, dev, window_us, rounds):
+    """``--tables fp8``: the 8-bit step against the bf16 step (interact.hip, unchanged) on the dequantised table and
+    the same ids, alternated; each one's share of its own read-the-rows-once roof."""
+    codes, exps, table = tables
+    g = torch.Generator(device=dev).manual_seed(B + D)
+    if dist == "zipf":
+        u = torch.rand((B, F), device=dev, generator=g).double()
+        ids = ((1.0 - u) ** (-1.0 / 0.05) - 1.0).clamp(0, rows - 1).to(torch.int32)
+    else:
+        ids = torch.randint(0, rows, (B, F), device=dev, generator=g, dtype=torch.int32)
+    dense = torch.randn((B, D), device=dev, generator=g).to(BF)
+    M = F + 1
+    pairs = [(i, j) for i in range(M) for j in range(i)]
+    wlog = D + len(pairs)
+    wout = -(-wlog // 8) * 8
+    meta = torch.tensor([(0, -1, 0)] + [(f * rows, f, rows) for f in range(F)], dtype=torch.int64).t().contiguous().to(dev)
+    lut = K.dot_interact_lut(M, pairs, D).to(dev)
+    outs = {k: torch.empty((B, wout), dtype=BF, device=dev) for k in ("interact", "interact_fp8")}
+    fns = {"interact": lambda: K.dot_interact(table, ids, meta, lut, wlog, dense, True, out=outs["interact"]),
+           "interact_fp8": lambda: K.dot_interact(codes, ids, meta, lut, wlog, dense, True, out=outs["interact_fp8"], table_exp=exps)}
+    shape = f"B{B}xF{F}xD{D}:{dist}"
+    t = alternate(fns, window_us, rounds)
+    same = torch.equal(outs["interact"].view(torch.int16), outs["interact_fp8"].view(torch.int16))
+    rest = D * 2 + wout * 2 + 4 * F
+    roofs = {"interact": B * (F * D * 2 + rest) / COPY_BYTES_PER_US, "interact_fp8": B * (F * (D + 1) + rest) / COPY_BYTES_PER_US}
+    for name, ts in t.items():
+        line(shape, name, ts, roof_us=round(roofs[name], 2), share_of_roof=round(roofs[name] / statistics.median(ts), 3))
+    print(json.dumps({"shape": shape, "fp8_over_bf16_time": round(statistics.median(t["interact_fp8"]) / statistics.median(t["interact"]), 3),
+                      "same_bits": same}), flush=True)
+
+
 def model(rows, dev, window_us, rounds):
     from flink_tensorflow_amd.graph.compiler import CompiledFunction
     from flink_tensorflow_amd.models.core import GraphDefGraphLoader
@@ -137,9 +191,19 @@ def main():
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--model", action="store_true")
     ap.add_argument("--model-rows", type=int, default=10_000)
+    ap.add_argument("--tables", choices=["bf16", "fp8"], default="bf16")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     F = 26
+    if a.tables == "fp8":  # the same shapes, 8-bit tables against bf16 tables of the same values
+        for F, D, Bs, dists in [(26, 64, (256, 2048, 32768), ("uniform", "zipf")), (26, 128, (256, 2048, 32768), ("uniform", "zipf"))] + \
+                ([(26, 80, (32768,), ("uniform",)), (26, 256, (32768,), ("uniform",)), (48, 128, (32768,), ("uniform",)), (48, 256, (32768,), ("uniform",))] if a.wide else []):
+            tables = fp8_tables(F, a.rows, D, dev)
+            for B in Bs:
+                for dist in dists:
+                    step_fp8(tables, B, F, D, a.rows, dist, dev, a.window_ms * 1e3, a.rounds)
+            del tables
+        return
     for D in (64, 128):
         table = torch.empty((F * a.rows, D), dtype=BF, device=dev).normal_()
         for B in (256, 2048, 32768):

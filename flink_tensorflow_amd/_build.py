@@ -140,7 +140,7 @@ def hip_flags() -> list[str]:
 # instructions (v_pk_add/mul/fma_f32), some forms of which round differently from the scalar
 # ones; the older files keep the flags they were measured with.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_FILE_FLAGS = {"retrieve.hip": _NO_PACKED_FP32, "interact.hip": _NO_PACKED_FP32,
+HIP_FILE_FLAGS = {"retrieve.hip": _NO_PACKED_FP32, "interact.hip": _NO_PACKED_FP32, "interact_fp8.hip": _NO_PACKED_FP32,
                   "attention_causal.hip": _NO_PACKED_FP32, "attention_causal_packed.hip": _NO_PACKED_FP32,
                   "attention_window.hip": _NO_PACKED_FP32}
 

@@ -142,9 +142,12 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
     def __init__(self, graph: Graph, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], device,
                  variables: dict | None = None, use_graph: bool = True, strict: bool = False,
                  topk_fetch: bool = True, precision: str = "bf16", calibration: dict | None = None,
-                 arena=None, token_capacity: int | None = None, pack_causal: bool = False):
+                 arena=None, token_capacity: int | None = None, pack_causal: bool = False,
+                 table_precision: str = "bf16"):
         if precision not in ("bf16", "fp8"):
             raise ValueError(f"precision must be bf16 or fp8, not {precision!r}")
+        if table_precision not in ("bf16", "fp8"):
+            raise ValueError(f"table_precision must be bf16 or fp8, not {table_precision!r}")
         from .control_flow import fold_static_control_flow
         from .functions import has_functional_ops, lower_functional_ops
 
@@ -165,6 +168,7 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
         self._cls_cache: dict[int, Val] = {}
         self.activation_bytes = 0
         self.precision = precision
+        self.table_precision = table_precision  # embedding tables of interact / embed steps (ranking_lowering.py)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             use_graph = False  # host plans run the fp32 reference ops (used by CPU tests)
@@ -195,7 +199,8 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
         if self._debug_sync or tracing.debug_poison():
             use_graph = False  # debug modes act between launches: run the plan eagerly
         if precision == "fp8":  # calibrate activation ranges on a bf16 twin of the plan
-            twin = CompiledFunction(graph, feeds, fetches, device, variables, use_graph=False, strict=strict)
+            twin = CompiledFunction(graph, feeds, fetches, device, variables, use_graph=False, strict=strict,
+                                    table_precision=table_precision)
             self._amax = twin.calibrate(calibration)
             del twin
 
@@ -1074,7 +1079,8 @@ class CompiledFunction(GeneratorLowering, TransformerLowering, DetectionLowering
 
 
 def compile_signature(session, feeds: dict[str, tuple[tuple, Any]], fetches: list[str], use_graph=True,
-                      strict=False, precision: str = "bf16", calibration: dict | None = None) -> CompiledFunction:
+                      strict=False, precision: str = "bf16", calibration: dict | None = None,
+                      table_precision: str = "bf16") -> CompiledFunction:
     """Compiles ``session``'s graph for the given feed shapes on the session's GPU."""
     return CompiledFunction(session.graph, feeds, fetches, session.device, session.variables, use_graph, strict,
-                            precision=precision, calibration=calibration)
+                            precision=precision, calibration=calibration, table_precision=table_precision)

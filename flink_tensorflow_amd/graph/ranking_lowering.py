@@ -30,6 +30,11 @@ A lone ``GatherV2(const [V, D] table, int32 ids, axis 0)`` with ``D % 8 == 0`` i
 step (``K.embed_rows``); when its only reader is a ``ConcatV2`` of such lookups on the last axis, the
 rows are written into the concat's slice in place.
 
+``CompiledFunction(..., table_precision="fp8")`` stores the tables of both steps as 8-bit tables
+(``K.quantize_table_fp8``: e4m3 codes and one power-of-two exponent per row, half the bytes) and the
+steps run ``kernels/interact_fp8.hip``; their meta carries ``"tables": "fp8"``.  A lone lookup with
+``D % 16 != 0`` keeps its bf16 table.  The option is independent of ``precision``.
+
 What stays glue (``CompileError`` under ``strict``): a fed or variable table, ``axis != 0``, int64
 ids; id columns of different feeds inside an interaction (the ``BatchMatMul`` stays glue, and so do
 the column ops); ``M > 64``, ``D`` outside the envelope, two activation vectors; ``Z`` or ``T`` with
@@ -170,6 +175,17 @@ class RankingLowering:
         return all(s in self.vals for s in (grp["ids"], grp["dense"]) if s is not None)
 
     # ------------------------------------------------------------------ lowering
+    def _table(self, table: torch.Tensor):
+        """The device form of a float ``[rows, D]`` table, interned as weights are: ``(bf16 table, None)``, or
+        under ``table_precision="fp8"`` and ``D % 16 == 0`` ``(e4m3 codes, row exponents)``.  A table with an
+        inf or NaN entry has no 8-bit form and stays bf16, as it lowers today."""
+        if self.table_precision == "fp8" and table.shape[1] % 16 == 0 and bool(torch.isfinite(table).all()):
+            stored = [self._dev(t) for t in K.quantize_table_fp8(table)]
+        else:
+            stored = [self._dev(table, torch.bfloat16), None]
+        self.params += [t for t in stored if t is not None]
+        return stored
+
     def _lower_interaction(self, node) -> bool:
         """``node`` ends a matched group: emits its ``interact`` step.  When the operands do not
         validate the members are lowered op by op, in order, and False lets ``node`` follow."""
@@ -214,10 +230,10 @@ class RankingLowering:
                                   or dense.dtype not in (torch.bfloat16, torch.float32, torch.uint8)):
             return False
         xin = self._as_bf16(dense, node.name) if dense is not None else None
-        table_dev = self._dev(torch.cat(tables), torch.bfloat16)
+        table_dev, exp_dev = self._table(torch.cat(tables))
         meta_dev = self._dev(torch.tensor(meta, dtype=torch.int64).t().contiguous())
         lut_dev = self._dev(K.dot_interact_lut(M, grp["pairs"], D if copy else 0))
-        self.params += [table_dev, meta_dev, lut_dev]
+        self.params += [meta_dev, lut_dev]
         wout = -(-wlog // 8) * 8
         out = self._new((B, wlog), phys_c=wout if wout != wlog else None)
         if wout != wlog:
@@ -225,10 +241,11 @@ class RankingLowering:
 
         def run(ids=ids, xin=xin, out=out):
             K.dot_interact(table_dev, _view(ids), meta_dev, lut_dev, wlog, _view(xin) if xin is not None else None, copy,
-                           out=out.buf)
+                           out=out.buf, table_exp=exp_dev)
 
         self._emit(node.name, "interact", run, [ids] + ([xin] if xin is not None else []), [out],
-                   {"M": M, "D": D, "width": wlog, "fields": M - (dense is not None)})
+                   {"M": M, "D": D, "width": wlog, "fields": M - (dense is not None),
+                    **({"tables": "fp8"} if exp_dev is not None else {})})
         self.vals[(node.name, 0)] = out
         return True
 
@@ -243,14 +260,14 @@ class RankingLowering:
                 or ids.phys_c or ids.rows is not None or not ids.shape or min(ids.shape) < 1:
             return False
         V, D = t.const.shape
-        table_dev = self._dev(t.const.float(), torch.bfloat16)
-        self.params.append(table_dev)
+        table_dev, exp_dev = self._table(t.const.float())
         out = self._new((*ids.shape, D))
 
         def run(ids=ids, out=out):  # a sole ConcatV2 reader: the rows go straight into its slice (``_lower_concat``)
             tgt, off = _target(out), _coff(out)
-            K.embed_rows(table_dev, _view(ids).reshape(-1), 0, V, out=tgt.view(-1, tgt.shape[-1])[:, off:off + D])
+            K.embed_rows(table_dev, _view(ids).reshape(-1), 0, V, out=tgt.view(-1, tgt.shape[-1])[:, off:off + D],
+                         table_exp=exp_dev)
 
-        self._emit(node.name, "embed", run, [ids], [out], {"V": V, "D": D})
+        self._emit(node.name, "embed", run, [ids], [out], {"V": V, "D": D, **({"tables": "fp8"} if exp_dev is not None else {})})
         self.vals[(node.name, 0)] = out
         return True

@@ -41,6 +41,7 @@ void register_instnorm(pybind11::module_& m);
 void register_pad(pybind11::module_& m);
 void register_retrieve(pybind11::module_& m);
 void register_interact(pybind11::module_& m);
+void register_interact_fp8(pybind11::module_& m);
 
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "flink_tensorflow_amd CDNA4 (gfx950) kernels";
@@ -77,6 +78,7 @@ PYBIND11_MODULE(_hip, m) {
   register_pad(m);
   register_retrieve(m);
   register_interact(m);
+  register_interact_fp8(m);
   // Streams owned by the framework (not torch's round-robin pool of 32 per device): a pooled
   // stream handed to a runner can be the very stream another thread is capturing a hipGraph
   // on, and then that thread's launches land in the capture (or are rejected).

@@ -95,8 +95,11 @@ class DLRMModel(GenericModel, BatchedGpuModel):
     def __init__(self, dense_features: int = 13, vocab_sizes: Sequence[int] = (1000,) * 26, dim: int = 128,
                  bottom: Sequence[int] = (512, 256, 128), top: Sequence[int] = (1024, 1024, 512, 256, 1),
                  buckets: Sequence[int] = (32, 256), seed: int = 0, weights: dict | None = None, device=None,
-                 use_graph: bool = True):
+                 use_graph: bool = True, table_precision: str = "bf16"):
         super().__init__(device)
+        if table_precision not in ("bf16", "fp8"):
+            raise ValueError(f"table_precision must be bf16 or fp8, not {table_precision!r}")
+        self.table_precision = table_precision  # "fp8": the plans keep the embedding tables as e4m3 codes + row exponents
         self.dense_features, self.vocab_sizes, self.dim = dense_features, tuple(vocab_sizes), dim
         self.bottom, self.top = tuple(bottom), tuple(top)
         self.buckets = tuple(sorted(buckets))
@@ -123,7 +126,8 @@ class DLRMModel(GenericModel, BatchedGpuModel):
             self._arena = DeviceArena(dev, EngineConfig().arena_bytes(dev), name=type(self).__name__)
             W, F = dlrm_dense_width(self.dense_features), len(self.vocab_sizes)
             self._plans = {b: CompiledFunction(self._session.graph, {"dense:0": ((b, W), "FLOAT"), "ids:0": ((b, F), "INT32")},
-                                               self.fetches, dev, use_graph=self.use_graph, strict=True, arena=self._arena)
+                                               self.fetches, dev, use_graph=self.use_graph, strict=True, arena=self._arena,
+                                               table_precision=self.table_precision)
                            for b in sorted(self.buckets, reverse=True)}
 
     def close(self) -> None:

@@ -1726,9 +1726,60 @@ def dot_interact_lut(M: int, pairs, first_col: int = 0) -> torch.Tensor:
     return lut
 
 
+# 8-bit tables (``kernels/interact_fp8.hip``): a row is ``D`` OCP e4m3fn codes and one power-of-two
+# exponent, ``value[r, d] = e4m3(codes[r, d]) * 2^exps[r]``.  With ``|exps| <= 32`` every value is
+# exactly a bf16, so the fp8 kernels give the bits of the bf16 kernels on the dequantised table.
+TABLE_FP8_EXP_MIN, TABLE_FP8_EXP_MAX = -32, 31
+
+
+def quantize_table_fp8(table: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(codes uint8 [rows, D], exps int8 [rows])`` of a finite ``[rows, D]`` table.  Per row the
+    exponent ``k`` is the smallest integer with ``amax <= 448 * 2^k``, clamped to ``[-32, 31]`` (0
+    for an all-zero row); the codes are ``x / 2^k`` rounded to nearest-even e4m3 and saturated to
+    ``+-448``, so the NaN codes 0x7F and 0xFF never appear."""
+    if table.dim() != 2 or not table.is_floating_point() or not bool(torch.isfinite(table).all()):
+        raise ValueError(f"quantize_table_fp8: table {tuple(table.shape)} {table.dtype} is not a finite float [rows, D]")
+    x = table.detach().to("cpu", torch.float64)
+    # amax = m 2^e with 0.5 <= m < 1 and 448 = 0.875 * 2^9: amax <= 448 * 2^k  <=>  m 2^(e - 9 - k) <= 0.875
+    m, e = torch.frexp(x.abs().amax(1) if x.shape[1] else x.new_zeros(len(x)))
+    k = torch.where(m > 0.875, e - 8, e - 9)
+    k = torch.where(m == 0, torch.zeros_like(k), k).clamp(TABLE_FP8_EXP_MIN, TABLE_FP8_EXP_MAX)
+    scaled = torch.ldexp(x, -k[:, None]).clamp(-448.0, 448.0)
+    codes = scaled.to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)  # float64 -> float32 is exact or far above 448
+    return codes.to(table.device), k.to(torch.int8).to(table.device)
+
+
+def dequantize_table_fp8(codes: torch.Tensor, exps: torch.Tensor) -> torch.Tensor:
+    """The bf16 ``[rows, D]`` table a ``quantize_table_fp8`` pair stands for (exact)."""
+    if codes.dim() != 2 or codes.dtype != torch.uint8 or exps.dtype != torch.int8 or tuple(exps.shape) != (codes.shape[0],):
+        raise ValueError(f"dequantize_table_fp8: codes {tuple(codes.shape)} {codes.dtype} / exps {tuple(exps.shape)} {exps.dtype} "
+                         "are not uint8 [rows, D] / int8 [rows]")
+    vals = codes.cpu().view(torch.float8_e4m3fn).to(torch.float32)
+    return torch.ldexp(vals, exps.cpu().to(torch.int32)[:, None]).to(torch.bfloat16).to(codes.device)
+
+
+def _table_fp8(name: str, table: torch.Tensor, table_exp: torch.Tensor | None) -> bool:
+    """Whether ``table`` is the codes of an 8-bit table; its exponents are checked with it.  Their range is
+    checked on the host only (a device check would synchronise every launch): on the GPU an exponent
+    outside ``[-32, 31]`` gives undefined values, never an address."""
+    if table.dtype != torch.uint8:
+        if table_exp is not None:
+            raise ValueError(f"{name}: table_exp goes with a uint8 table of e4m3 codes, not with {table.dtype}")
+        return False
+    if table_exp is None or table_exp.dtype != torch.int8 or tuple(table_exp.shape) != (table.shape[0],) \
+            or table_exp.device != table.device:
+        raise ValueError(f"{name}: a uint8 table needs table_exp, int8 [{table.shape[0]}] on the table's device")
+    if table.shape[1] % 16:
+        raise ValueError(f"{name}: an 8-bit table has D % 16 == 0, not D = {table.shape[1]}")
+    if not table_exp.is_cuda and table_exp.numel() and \
+            not TABLE_FP8_EXP_MIN <= int(table_exp.min()) <= int(table_exp.max()) <= TABLE_FP8_EXP_MAX:
+        raise ValueError(f"{name}: table_exp outside [{TABLE_FP8_EXP_MIN}, {TABLE_FP8_EXP_MAX}]")
+    return True
+
+
 def dot_interact(table: torch.Tensor, ids: torch.Tensor, meta: torch.Tensor, lut: torch.Tensor, width: int,
                  dense: torch.Tensor | None = None, copy_dense: bool = False, out: torch.Tensor | None = None,
-                 workgroups: int | None = None):
+                 workgroups: int | None = None, *, table_exp: torch.Tensor | None = None):
     """The input row of a DLRM top MLP.  Per record ``b`` the ``M`` vectors ``T[m]`` are gathered:
     ``meta`` is int64 ``[3, M]`` = (first table row of the vector's field, its column in ``ids``
     or -1 for the activation vector, the field's vocabulary size ``V``), so ``T[m] =
@@ -1743,10 +1794,15 @@ def dot_interact(table: torch.Tensor, ids: torch.Tensor, meta: torch.Tensor, lut
     ``GatherV2`` raises there, its GPU kernel returns zeros).  ``out`` is a preallocated bf16
     ``[B, Wout]`` view with unit column stride and any row pitch (a concat slot): a captured
     launch passes it.  ``workgroups`` is the grid of 4-wave workgroups, a wave striding over the
-    records (default: a wave per record, ``INTERACT_MAX_WORKGROUPS`` at most)."""
+    records (default: a wave per record, ``INTERACT_MAX_WORKGROUPS`` at most).
+
+    A uint8 ``table`` holds the e4m3 codes of an 8-bit table and ``table_exp`` its int8 row
+    exponents (``quantize_table_fp8``): the same result, bit for bit, as with the dequantised
+    table, from ``kernels/interact_fp8.hip``."""
     if table.dim() != 2 or ids.dim() != 2 or meta.dim() != 2 or meta.shape[0] != 3:
         raise ValueError(f"dot_interact: table {tuple(table.shape)} / ids {tuple(ids.shape)} / meta {tuple(meta.shape)} "
                          "are not [rows, D] / [B, F] / [3, M]")
+    fp8 = _table_fp8("dot_interact", table, table_exp)
     (rows, D), (B, F), M, width = table.shape, ids.shape, meta.shape[1], int(width)
     wout = -(-width // 8) * 8
     if not dot_interact_eligible(M, D, width) or B < 1:
@@ -1761,6 +1817,8 @@ def dot_interact(table: torch.Tensor, ids: torch.Tensor, meta: torch.Tensor, lut
     if out is not None and (out.dim() != 2 or tuple(out.shape) != (B, wout) or out.stride(1) != 1):
         raise ValueError(f"dot_interact: out {tuple(out.shape)} is not a [{B}, {wout}] view with unit column stride")
     if not table.is_cuda:
+        if fp8:
+            table = dequantize_table_fp8(table, table_exp)
         mt = meta.long()
         T = torch.zeros((B, _interact_mpad(M), D), dtype=torch.float32)  # the LUT indexes the padded Z
         for m in range(M):
@@ -1784,7 +1842,7 @@ def dot_interact(table: torch.Tensor, ids: torch.Tensor, meta: torch.Tensor, lut
         out.copy_(res)
         return out
     dev = table.device
-    _check(table, "table", torch.bfloat16, dev)
+    _check(table, "table", torch.uint8 if fp8 else torch.bfloat16, dev)
     _check(meta, "meta", torch.int64, dev)
     _check(lut, "lut", torch.int16, dev)
     if ids.dtype != torch.int32 or ids.device != dev or ids.stride(1) != 1:
@@ -1795,26 +1853,36 @@ def dot_interact(table: torch.Tensor, ids: torch.Tensor, meta: torch.Tensor, lut
         out = torch.empty((B, wout), dtype=torch.bfloat16, device=dev)
     if out.dtype != torch.bfloat16 or out.device != dev:
         raise ValueError("dot_interact: out must be bf16 on the table's device")
-    _hip().dot_interact(table.data_ptr(), rows, ids.data_ptr(), ids.stride(0), F, meta.data_ptr(), lut.data_ptr(),
-                        _ptr(dense), dense.stride(0) if dense is not None else 0, int(bool(copy_dense)), B, M, D, width,
-                        out.data_ptr(), out.stride(0),
-                        min(-(-B // 4), INTERACT_MAX_WORKGROUPS) if workgroups is None else int(workgroups), _stream())
+    rest = (rows, ids.data_ptr(), ids.stride(0), F, meta.data_ptr(), lut.data_ptr(),
+            _ptr(dense), dense.stride(0) if dense is not None else 0, int(bool(copy_dense)), B, M, D, width,
+            out.data_ptr(), out.stride(0),
+            min(-(-B // 4), INTERACT_MAX_WORKGROUPS) if workgroups is None else int(workgroups), _stream())
+    if fp8:
+        _check(table_exp, "table_exp", torch.int8, dev)
+        _hip().dot_interact_fp8(table.data_ptr(), table_exp.data_ptr(), *rest)
+    else:
+        _hip().dot_interact(table.data_ptr(), *rest)
     return out
 
 
 def embed_rows(table: torch.Tensor, ids: torch.Tensor, base: int = 0, vocab: int | None = None,
-               out: torch.Tensor | None = None):
+               out: torch.Tensor | None = None, *, table_exp: torch.Tensor | None = None):
     """``out[r, :] = table[base + ids[r]]`` as bf16 for the flattened int32 ``ids``: a plain
     embedding lookup in the field whose ``vocab`` rows start at row ``base`` of the bf16 ``table
     [rows, D]``, ``D % 8 == 0``.  An id outside ``[0, vocab)`` gives a zero row.  ``out`` is a
-    preallocated bf16 ``[R, D]`` view with unit column stride and any row pitch (a concat slot)."""
+    preallocated bf16 ``[R, D]`` view with unit column stride and any row pitch (a concat slot).
+    A uint8 ``table`` with ``table_exp`` is an 8-bit table (``quantize_table_fp8``, ``D % 16 == 0``):
+    the rows of the dequantised table."""
     if table.dim() != 2 or table.shape[1] % 8 or ids.numel() < 1:
         raise ValueError(f"embed_rows: table {tuple(table.shape)} is not [rows, D] with D % 8 == 0, or no ids")
+    fp8 = _table_fp8("embed_rows", table, table_exp)
     (rows, D), R = table.shape, ids.numel()
     vocab = rows - base if vocab is None else int(vocab)
     if out is not None and (out.dim() != 2 or tuple(out.shape) != (R, D) or out.stride(1) != 1):
         raise ValueError(f"embed_rows: out {tuple(out.shape)} is not a [{R}, {D}] view with unit column stride")
     if not table.is_cuda:
+        if fp8:
+            table = dequantize_table_fp8(table, table_exp)
         i = ids.reshape(-1).long()
         ok = (i >= 0) & (i < vocab) & (base + i >= 0) & (base + i < rows)
         res = torch.where(ok[:, None], table[(base + i).clamp(0, rows - 1)].float(), 0.0).to(torch.bfloat16)
@@ -1823,14 +1891,18 @@ def embed_rows(table: torch.Tensor, ids: torch.Tensor, base: int = 0, vocab: int
         out.copy_(res)
         return out
     dev = table.device
-    _check(table, "table", torch.bfloat16, dev)
+    _check(table, "table", torch.uint8 if fp8 else torch.bfloat16, dev)
     _check(ids, "ids", torch.int32, dev)
     if out is None:
         out = torch.empty((R, D), dtype=torch.bfloat16, device=dev)
     if out.dtype != torch.bfloat16 or out.device != dev:
         raise ValueError("embed_rows: out must be bf16 on the table's device")
-    _hip().embed_rows(table.data_ptr(), rows, ids.data_ptr(), int(base), vocab, R, D, out.data_ptr(), out.stride(0),
-                      _stream())
+    rest = (rows, ids.data_ptr(), int(base), vocab, R, D, out.data_ptr(), out.stride(0), _stream())
+    if fp8:
+        _check(table_exp, "table_exp", torch.int8, dev)
+        _hip().embed_rows_fp8(table.data_ptr(), table_exp.data_ptr(), *rest)
+    else:
+        _hip().embed_rows(table.data_ptr(), *rest)
     return out
 
 
